@@ -24,6 +24,9 @@ is the scan kernel (HIP-event timed inside the engine on its launch stream); at 
                   Neither host-inclusive rate is `value`.
   `config5`       BASELINE config 5 through the product command line: a directory of synthetic genomes as multi-FASTA files,
                   no -A, L3K10 and L2K11 (genomes/s and Gbases/s by the parent's clock; --no-config5 skips it).
+
+--dump-outputs DIR writes the sketch of the LAST timed step -- what a caller of the library receives -- as .npy files under DIR
+(dump_outputs()), so that two builds run with the same arguments (the same seeded reads) can be compared output for output.
 """
 import argparse
 import hashlib
@@ -929,6 +932,51 @@ def sketch_digest(ids, counts):
     return h.hexdigest()
 
 
+DUMP_BUDGET = 64 << 20  # bytes of .npy data at most under --dump-outputs
+
+
+def result_arrays(r):
+    """an engine-owned result (capi.ResultC) -> list over components of (ids u32, counts u16 or None), copied out"""
+    import numpy as np
+    out = []
+    for c in range(r.component_num):
+        comp = r.components[c]
+        ids = np.ctypeslib.as_array(comp.ids, shape=(comp.n,)).copy() if comp.n else np.zeros(0, np.uint32)
+        cnt = (np.ctypeslib.as_array(comp.counts, shape=(comp.n,)).copy() if comp.n else np.zeros(0, np.uint16)) if comp.counts else None
+        out.append((ids, cnt))
+    return out
+
+
+def dump_outputs(d, sketch):
+    """--dump-outputs: per component c, sketch_c<c>_ids.npy (float64, which holds every u32 id exactly) and sketch_c<c>_counts.npy
+    (float32) in the order the library hands them out, and sketch_sizes.npy (distinct keys per component).  Where all of it would
+    exceed DUMP_BUDGET, every component keeps the same share of its entries, at positions drawn with a fixed seed (ascending) and
+    written as sketch_c<c>_positions.npy.  -> what the line reports about the dump"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sizes = [len(ids) for ids, _ in sketch]
+    total = sum(sizes)
+    per_entry = 8 + 4 * any(cnt is not None for _, cnt in sketch)  # an id (+ its count)
+    room = DUMP_BUDGET - (1 << 20)  # the rest: .npy headers and sketch_sizes.npy
+    share = 1.0 if total * per_entry <= room else room / float(total * (per_entry + 8))  # + 8: a sampled entry's position
+    files = ["sketch_sizes.npy"]
+    np.save(os.path.join(d, "sketch_sizes.npy"), np.array(sizes, dtype=np.float64))
+    for c, (ids, cnt) in enumerate(sketch):
+        if share < 1.0:
+            at = np.sort(np.random.RandomState(SEED + c).choice(len(ids), int(len(ids) * share), replace=False))
+            ids, cnt = ids[at], (None if cnt is None else cnt[at])
+            np.save(os.path.join(d, "sketch_c%d_positions.npy" % c), at.astype(np.float64))
+            files.append("sketch_c%d_positions.npy" % c)
+        np.save(os.path.join(d, "sketch_c%d_ids.npy" % c), ids.astype(np.float64))
+        files.append("sketch_c%d_ids.npy" % c)
+        if cnt is not None:
+            np.save(os.path.join(d, "sketch_c%d_counts.npy" % c), cnt.astype(np.float32))
+            files.append("sketch_c%d_counts.npy" % c)
+    return {"dir": d, "files": files, "distinct_keys": total, "sampled": share < 1.0,
+            "what": "the sketch of the last timed step (ids as float64, counts as float32, in the library's order)" +
+                    ("; a seeded sample of %.4f of every component's entries, positions in sketch_c<c>_positions.npy" % share if share < 1.0 else "")}
+
+
 def leg_inproc_multi(torch, capi, shuf, devices, total_reads, steps, merge, reference_sketch):
     """the C product's own multi-GPU path in THIS process: libmetakssd_multi.so (what `metakssd dist --devices` runs on) -- one engine
     per listed GPU, every engine scans its contiguous read range out of its GPU's HBM, mk_multi_finish merges (RCCL grouped
@@ -1141,12 +1189,19 @@ def main():
                          "speedup and efficiency")
     ap.add_argument("--verify", action="store_true",
                     help="after timing, rank 0 re-sketches ALL ranks' reads on one engine and compares with the merged result")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the sketch of the last one under DIR as .npy files (float64 ids, float32 counts; "
+                         "a seeded sample above 64 MB)")
     ap.add_argument("--inproc-child", default=None,
                     help="(internal) run ONLY the libmetakssd_multi.so leg on this comma-separated device list and print its JSON: rank 0 of an N > 1 run "
                          "starts this as a child process so that an RCCL that hangs or dies there cannot take the bench line with it")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 300 if args.gpus == 1 else 40
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs is not None and args.split_leg_only:
+        raise SystemExit("--dump-outputs: the split-queue profiling flow (--split-leg-only) keeps no result")
     if args.inproc_child is not None:
         import torch
         from metakssd_amd import capi
@@ -1352,7 +1407,11 @@ def main():
         if flags.get("pending"):
             r = eng.finish_end_raw()
             result["distinct"] = int(r.total)
-            capi.lib.mk_result_release(eng.h, r)
+            if flags.get("hold"):  # --dump-outputs: the last timed step's result, copied out after the clock has stopped
+                result["held"] = r
+                flags["hold"] = False
+            else:
+                capi.lib.mk_result_release(eng.h, r)
             flags["pending"] = False
 
     def fence():
@@ -1453,8 +1512,13 @@ def main():
         t0 = time.perf_counter()
         for _ in range(k):
             step()
+        flags["hold"] = args.dump_outputs is not None and rank == 0
         fence()
         dt = time.perf_counter() - t0
+        if "held" in result:
+            r = result.pop("held")
+            result["dump"] = result_arrays(r)
+            capi.lib.mk_result_release(eng.h, r)
         pr = eng.profile()
         eng.profile_enable(False)
         return dt, pr
@@ -1729,6 +1793,8 @@ def main():
             line["merged_equals_single_engine"] = bool(verified)
             if "verify_detail" in result:
                 line["verify_detail"] = result["verify_detail"]
+        if args.dump_outputs is not None:
+            line["dump_outputs"] = dump_outputs(args.dump_outputs, result.pop("dump"))
         if args.backend != "nccl":
             line["config"]["parallelism"] += " (debug transport: %s%s)" % (args.backend, ", same device" if args.same_device else "")
         if world == 1 and not args.no_host_legs:

@@ -141,7 +141,7 @@ def test_product_cli_reproduces_reference_golden(case, shuf_files, tmp_path):
     check_against_golden(case, out, inp)
 
 
-REF_HIP = os.path.join(ROOT, "oracle", "_ref_hip", "metakssd")
+REF_HIP = os.path.join(ROOT, "oracle", "_ref", "hip", "metakssd")
 
 
 @pytest.mark.gpu
@@ -240,12 +240,12 @@ def test_product_cli_packed_rows_equal_text_rows(shuf, flags, shuf_files, tmp_pa
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", sorted(MANIFEST["cases"]))
 def test_reference_program_with_dropin_tu_reproduces_golden(case, shuf_files, tmp_path):
-    """oracle/_ref_hip/metakssd = the reference's own translation units (its main, option parser, dist_dispatch, run_stageI
+    """oracle/_ref/hip/metakssd = the reference's own translation units (its main, option parser, dist_dispatch, run_stageI
     with the per-component concatenation and cofiles.stat, command_dist.c:341-500) linked with integration/iseq2comem_hip.c
     in place of iseq2comem.c (oracle/Makefile, target ref_hip): the library is a drop-in under the reference's call sites
     (command_dist.c:380-398), and the sketch directories are the ones the unmodified reference wrote"""
     if not os.path.exists(REF_HIP):
-        pytest.skip("oracle/_ref_hip/metakssd not built (needs the reference sources: make -C oracle ref_hip)")
+        pytest.skip("oracle/_ref/hip/metakssd not built (needs the reference sources: make -C oracle ref_hip)")
     entry = MANIFEST["cases"][case]
     inp = gc.build_input(case, str(tmp_path))
     out = str(tmp_path / "out")
