@@ -31,6 +31,8 @@
  *   get_species_abundance() dictionary + lookups     command_composite.c:525-553     mk_setop_join
  *   combco2mco() inverted index                      co2mco.c:37-66                  mk_mco_build / mk_mco_index_rows
  *   mco_cbdco_nobin_dist() counting loop             command_dist.c:1033-1049        mk_mco_count_begin/add/finish
+ *   index_abv() species-major matrix                 command_composite.c:347-440     mk_abv_index
+ *   abv_search() accumulation + qsort                command_composite.c:212-344     mk_abv_load / mk_abv_search
  *   dist_print_nobin() / output_ctrl()               command_dist.c:1531-1690        mk_dist_print
  *
  * Conventions: plain pointers and sizes only; every function returns MK_OK (0) or a negative
@@ -594,6 +596,44 @@ int mk_mco_count_finish(mk_mco *m, uint32_t *ct);
 /* measurement (bench.py's `next_rows` leg): device time of the last build's radix sort and of the last count_add's kernels, from HIP
  * events on the handle's stream -- the loops they replace are co2mco.c:37-59 and command_dist.c:1035-1048 */
 int mk_mco_last_kernel_ms(mk_mco *m, double *sort_ms, double *count_ms);
+
+/* ---- abundance-vector index and search: `composite -i` / `composite -s` ------------------------------------------
+ * An .abv file (written by `composite -q -b`) is a list of binVec_t {int32 ref_idx; float pct} (command_composite.h:12-16).
+ * index_abv() (command_composite.c:347-440) turns the files of <ref>/abundance_Vec into a species-major matrix;
+ * abv_search() (:212-344) ranks the indexed samples against query vectors by cosine (metric 0), L1 (1) or L2 (2).
+ *   mk_abv_index        = the realloc/append loop + counts + norms   :376-434   (stable sort of (species, position) by species)
+ *   mk_abv_load         = reading the four index files               :214-252   (kept resident on the device)
+ *   mk_abv_search       = accumulation, finish and qsort per query   :254-335
+ * Result pointers are library-owned pinned host memory, valid until the next call of the same kind or destroy.  There is
+ * no CPU path: mk_abv_create fails with MK_ERR_NO_DEVICE without a HIP device. */
+typedef struct mk_binvec {
+  int32_t ref_idx; /* species (in a .abv) or sample (in .abm) */
+  float pct;
+} mk_binvec;
+typedef struct mk_abv mk_abv;
+int mk_abv_create(int device, mk_abv **out);
+int mk_abv_destroy(mk_abv *a);
+const char *mk_abv_last_error(const mk_abv *a); /* a may be NULL: last error of a failed create */
+/* entries[n]: every file's vector, concatenated in directory order; file_end[nfiles]: cumulative ends; nref = infile_num of
+ * <ref>/cofiles.stat.  Returns abm[n] (= abundance_Vec.abm: per species in order, {file number, pct} by file, then by position
+ * in the file), abmi[nref] (= .abmi: int32 cumulative counts) and yl2n[nfiles] (= .yl2n: sqrt of the double sum of the float
+ * squares, in file order).  MK_ERR_FORMAT when a species lies outside 0..nref-1 (*bad_file = its file; the reference writes out
+ * of bounds there); MK_ERR_ARG above 2^31-1 entries. */
+int mk_abv_index(mk_abv *a, const mk_binvec *entries, uint64_t n, const uint64_t *file_end, uint32_t nfiles, uint32_t nref,
+                 const mk_binvec **abm, const int32_t **abmi, const double **yl2n, int64_t *bad_file);
+/* the four index files: abm[n], abmi[nref] (from the .abmi size), yl2n[nsamples] (nsamples = lines of .name).  MK_ERR_FORMAT when
+ * .abmi does not ascend inside 0..n, or a column names a sample >= nsamples or does not ascend (not an index made by -i). */
+int mk_abv_load(mk_abv *a, const mk_binvec *abm, uint64_t n, const int32_t *abmi, uint32_t nref, const double *yl2n,
+                uint32_t nsamples);
+/* nq query vectors (q concatenated, q_end[nq] cumulative) against the loaded index.  For query k the matched samples are
+ * samples[out_end[k-1] .. out_end[k]) with their float measures, in the order the reference prints them: the reference's
+ * qsort order (stable by measure over the discovery order), reversed for cosine.  The measure is the float the reference
+ * sorts by: for L2 the sum of squares (it prints the sqrt).  MK_ERR_FORMAT when a query species lies outside the index
+ * (*bad_query = the query); MK_ERR_ARG when nq * nsamples >= 2^32. */
+int mk_abv_search(mk_abv *a, int metric, uint32_t nq, const mk_binvec *q, const uint64_t *q_end, uint64_t *out_end,
+                  const int32_t **samples, const float **measures, int64_t *bad_query);
+/* measurement: device time of the last index's and the last search's kernels, from HIP events on the handle's stream */
+int mk_abv_last_kernel_ms(mk_abv *a, double *index_ms, double *search_ms);
 
 /* distance.out (host).  Options as command_dist_wrapper.c:83-92. */
 typedef struct mk_dist_opts {

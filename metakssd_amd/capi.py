@@ -190,6 +190,12 @@ def _load():
         "mk_mco_count_add": [vp, vp, u64, vp, vp, vp, vp, vp],
         "mk_mco_count_finish": [vp, vp],
         "mk_mco_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+        "mk_abv_create": [C.c_int, C.POINTER(vp)],
+        "mk_abv_destroy": [vp],
+        "mk_abv_index": [vp, vp, u64, vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)],
+        "mk_abv_load": [vp, vp, u64, vp, u32, vp, u32],
+        "mk_abv_search": [vp, C.c_int, u32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)],
+        "mk_abv_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "mk_dist_print": [vp, C.POINTER(DistOptsC), i32, i32, u32, u32, vp, vp, vp, vp, vp],
         "mk_sketchdir_open": [C.c_char_p, C.POINTER(ParamsC), C.c_int, C.c_int, C.POINTER(vp)],
         "mk_sketchdir_add": [vp, C.c_char_p, C.POINTER(ResultC)],
@@ -205,6 +211,8 @@ def _load():
     lib.mk_setop_last_error.restype = C.c_char_p
     lib.mk_mco_last_error.argtypes = [vp]
     lib.mk_mco_last_error.restype = C.c_char_p
+    lib.mk_abv_last_error.argtypes = [vp]
+    lib.mk_abv_last_error.restype = C.c_char_p
     lib.mk_setop_stream.argtypes = [vp]
     lib.mk_setop_stream.restype = vp
     lib.mk_last_error.argtypes = [vp]
@@ -974,6 +982,80 @@ class Mco:
                 lib.mk_host_free(self._slab)
                 self._slab, self._slab_cap = None, 0
             lib.mk_mco_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+BINVEC = np.dtype([("ref_idx", "<i4"), ("pct", "<f4")])  # mk_binvec = binVec_t (command_composite.h:12-16), the records of a .abv
+
+
+class Abv:
+    """abundance-vector index and search on the device (mk_abv_*: `composite -i` / `composite -s`, command_composite.c:212-440)"""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        rc = lib.mk_abv_create(device, C.byref(self.h))
+        if rc:
+            raise MkError(rc, (lib.mk_abv_last_error(None) or b"").decode())
+
+    def _check(self, rc):
+        if rc:
+            raise MkError(rc, (lib.mk_abv_last_error(self.h) or b"").decode())
+
+    def index(self, vectors, nref):
+        """vectors: the files' BINVEC arrays in directory order -> (abm BINVEC[n], abmi int32[nref], yl2n float64[len(vectors)]),
+        the contents of abundance_Vec.{abm,abmi,yl2n}.  MkError(MK_ERR_FORMAT) names the file of a species outside 0..nref-1."""
+        vs = [np.ascontiguousarray(v).view(BINVEC) for v in vectors]
+        ent = np.ascontiguousarray(np.concatenate(vs) if vs else np.zeros(0, BINVEC))
+        ends = np.cumsum([len(v) for v in vs], dtype=np.uint64) if vs else np.zeros(0, np.uint64)
+        abm, abmi, yl2n, bad = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64(-1)
+        self._check(lib.mk_abv_index(self.h, ent.ctypes.data if ent.size else None, ent.size, ends.ctypes.data if ends.size else None,
+                                     len(vs), nref, C.byref(abm), C.byref(abmi), C.byref(yl2n), C.byref(bad)))
+
+        def arr(p, dt, k):
+            if not k:
+                return np.zeros(0, dt)
+            return np.frombuffer((C.c_char * (k * np.dtype(dt).itemsize)).from_address(p.value), dtype=dt).copy()
+        return arr(abm, BINVEC, ent.size), arr(abmi, np.int32, nref), arr(yl2n, np.float64, len(vs))
+
+    def load(self, abm, abmi, yl2n):
+        """keep an index resident on the device (nsamples = len(yl2n))"""
+        abm = np.ascontiguousarray(abm).view(BINVEC)
+        abmi = np.ascontiguousarray(abmi, dtype=np.int32)
+        yl2n = np.ascontiguousarray(yl2n, dtype=np.float64)
+        self._check(lib.mk_abv_load(self.h, abm.ctypes.data if abm.size else None, abm.size, abmi.ctypes.data if abmi.size else None,
+                                    abmi.size, yl2n.ctypes.data if yl2n.size else None, yl2n.size))
+
+    def search(self, metric, queries):
+        """metric 0 cosine / 1 L1 / 2 L2; queries: BINVEC arrays -> per query (sample ids int32, float32 measures) in the order
+        the reference prints them (for L2 the measure is the sum of squares; it prints the sqrt)"""
+        qs = [np.ascontiguousarray(q).view(BINVEC) for q in queries]
+        ent = np.ascontiguousarray(np.concatenate(qs) if qs else np.zeros(0, BINVEC))
+        ends = np.cumsum([len(q) for q in qs], dtype=np.uint64) if qs else np.zeros(0, np.uint64)
+        oend = np.zeros(max(len(qs), 1), np.uint64)
+        ids, ms, bad = C.c_void_p(), C.c_void_p(), C.c_int64(-1)
+        self._check(lib.mk_abv_search(self.h, metric, len(qs), ent.ctypes.data if ent.size else None, ends.ctypes.data if ends.size else None,
+                                      oend.ctypes.data, C.byref(ids), C.byref(ms), C.byref(bad)))
+        out, lo = [], 0
+        for k in range(len(qs)):
+            hi = int(oend[k])
+            if hi > lo:
+                i = np.frombuffer((C.c_char * (4 * hi)).from_address(ids.value), dtype=np.int32)[lo:hi].copy()
+                m = np.frombuffer((C.c_char * (4 * hi)).from_address(ms.value), dtype=np.float32)[lo:hi].copy()
+            else:
+                i, m = np.zeros(0, np.int32), np.zeros(0, np.float32)
+            out.append((i, m))
+            lo = hi
+        return out
+
+    def last_kernel_ms(self):
+        """(kernels of the last index, kernels of the last search) in ms, from the handle's HIP events"""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self._check(lib.mk_abv_last_kernel_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if self.h:
+            lib.mk_abv_destroy(self.h)
             self.h = C.c_void_p()
 
 

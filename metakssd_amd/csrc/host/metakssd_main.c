@@ -8,13 +8,12 @@
  * (cofiles.stat, combco.N, combco.index.N, combco.N.a).
  *
  * Also built, each on the device behind the same C ABI: FASTQ without -A (-n / -Q, fastq2co), `set -u|-q|-i|-s|-g|-c|-P`,
- * `composite -r -q [-b]` / `-d`, stage II (`dist -o <mco> <sketch dir>`, `dist -L .. -r <genomes> -o <db>`) and the
+ * `composite -r -q [-b]` / `-d` / `-i` / `-s <0|1|2>`, stage II (`dist -o <mco> <sketch dir>`, `dist -L .. -r <genomes> -o <db>`) and the
  * database search `dist -r <mco> -o <out> [-M -O -N -D --correction --keepskf -f] <sketch dir>`.
  *
  * Differences, all documented in DESIGN.md: inputs are processed in discovery order (the reference
- * applies a time-seeded shuffle, command_dist.c:215); --byread, composite -i/-s and reverse are not
- * part of this build; -p N sets the number of host threads that read and frame/window input files ahead of the GPU
- * (default 8); --device selects the GPU.
+ * applies a time-seeded shuffle, command_dist.c:215); --byread and reverse are not part of this build; -p N sets the
+ * number of host threads that read and frame/window input files ahead of the GPU (default 8); --device selects the GPU.
  */
 #define _GNU_SOURCE
 #include "metakssd_hip.h"
@@ -24,6 +23,7 @@
 #include <dirent.h>
 #include <dlfcn.h>
 #include <errno.h>
+#include <math.h>
 #include <pthread.h>
 #include <signal.h>
 #include <spawn.h>
@@ -869,6 +869,8 @@ static void usage(void) {
           "       metakssd set -u|-q|-i <pan dir>|-s <pan dir>|-g <tax.tsv>|-c|-P [-o outdir] [--device D] <sketch dir>\n"
           "       metakssd composite -r <marker db dir> -q <-A sketch dir> [-b] [-o outdir] [--device D]\n"
           "       metakssd composite -d <x.abv>...\n"
+          "       metakssd composite -r <marker db dir> -i [--device D]                 (index <dir>/abundance_Vec/*.abv)\n"
+          "       metakssd composite -r <marker db dir> -s <0|1|2> [--device D] <x.abv>...  (0 cosine, 1 L1, 2 L2)\n"
           "       metakssd shuffle -k <halfK> -s <halfSubK> -l <level> [--seed N] -o <prefix>\n");
   exit(2);
 }
@@ -1321,6 +1323,244 @@ static int composite_read_abv(int nfiles, char **files) {
   return 1;
 }
 
+/* ---- `composite -r <ref> -i` / `composite -r <ref> -s <0|1|2> <x.abv>...`: index_abv() and abv_search(),
+ * command_composite.c:347-440 and :212-344.  The index (a stable sort by species) and the search (accumulation, ordering)
+ * run on the device (mk_abv_*); reading the files and printing stay here. */
+static int abv_name_ok(const char *name) { /* strrchr(name,'.') + 1 == "abv"; a name without a dot crashes the reference */
+  const char *ext = strrchr(name, '.');
+  return ext && strcmp(ext + 1, "abv") == 0;
+}
+
+static int composite_index(const char *refdir, int device) {
+  char dpath[PATHLEN * 2 + 32], path[PATHLEN * 3 + 64];
+  snprintf(dpath, sizeof dpath, "%s/abundance_Vec", refdir);
+  DIR *dir = opendir(dpath);
+  if (!dir) die("index_abv(): %s does not exists! ", dpath);
+  snprintf(path, sizeof path, "%s/cofiles.stat", refdir);
+  size_t sn = 0;
+  uint8_t *st = read_whole(path, &sn);
+  if (!st || sn < 32) die("cannot find cofiles.stat under %s ", refdir);
+  int32_t nref;
+  memcpy(&nref, st + 20, 4);
+  free(st);
+  if (nref < 0) die("index_abv(): %s: infile_num %d", path, nref);
+  /* readdir order, unsorted, as the reference walks it (:379) */
+  size_t nf = 0, fcap = 64, ncap = 1 << 16, nlen = 0, ecap = 1 << 16;
+  uint64_t n = 0, *fend = malloc(8 * fcap);
+  char *names = malloc(ncap);
+  mk_binvec *ent = malloc(sizeof(mk_binvec) * ecap);
+  struct dirent *de;
+  while ((de = readdir(dir)) != NULL) {
+    if (!abv_name_ok(de->d_name)) continue;
+    snprintf(path, sizeof path, "%s/%s", dpath, de->d_name);
+    struct stat fs;
+    FILE *f = fopen(path, "rb");
+    if (!f || fstat(fileno(f), &fs) != 0) die("index_abv():%s", path);
+    const uint64_t len = (uint64_t)fs.st_size / sizeof(mk_binvec);
+    if (n + len > 0x7FFFFFFFull) die("index_abv(): more than 2^31-1 entries (.abmi holds int32 counts)");
+    if (n + len > ecap) {
+      while (n + len > ecap) ecap *= 2;
+      ent = realloc(ent, sizeof(mk_binvec) * ecap);
+    }
+    if (len && fread(ent + n, sizeof(mk_binvec), len, f) != len) die("index_abv():%s", path);
+    fclose(f);
+    n += len;
+    if (nf == fcap) { fcap *= 2; fend = realloc(fend, 8 * fcap); }
+    fend[nf++] = n;
+    const size_t l = strlen(de->d_name);
+    if (nlen + l + 2 > ncap) { while (nlen + l + 2 > ncap) ncap *= 2; names = realloc(names, ncap); }
+    memcpy(names + nlen, de->d_name, l);
+    names[nlen + l] = '\n';
+    nlen += l + 1;
+  }
+  closedir(dir);
+  if (!ent || !fend || !names) die("index_abv(): out of memory");
+  mk_abv *a;
+  if (mk_abv_create(device, &a) != MK_OK) die("mk_abv_create failed: %s", mk_abv_last_error(NULL));
+  const mk_binvec *abm;
+  const int32_t *abmi;
+  const double *yl2n;
+  int64_t bad = -1;
+  if (mk_abv_index(a, ent, n, fend, (uint32_t)nf, (uint32_t)nref, &abm, &abmi, &yl2n, &bad) != MK_OK) {
+    if (bad >= 0) { /* the bad_file-th name */
+      const char *nm = names;
+      for (int64_t k = 0; k < bad; k++) nm = strchr(nm, '\n') + 1;
+      die("index_abv(): %s/%.*s: %s", dpath, (int)(strchr(nm, '\n') - nm), nm, mk_abv_last_error(a));
+    }
+    die("index_abv(): %s", mk_abv_last_error(a));
+  }
+  static const char *suf[4] = {"name", "yl2n", "abm", "abmi"};
+  const void *data[4] = {names, yl2n, abm, abmi};
+  const size_t bytes[4] = {nlen, 8 * nf, sizeof(mk_binvec) * n, 4 * (size_t)nref};
+  for (int k = 0; k < 4; k++) {
+    snprintf(path, sizeof path, "%s/abundance_Vec.%s", refdir, suf[k]);
+    FILE *f = fopen(path, "wb");
+    if (!f || (bytes[k] && fwrite(data[k], 1, bytes[k], f) != bytes[k]) || fclose(f) != 0) die("index_abv():%s", path);
+  }
+  mk_abv_destroy(a);
+  free(ent); free(fend); free(names);
+  return 0;
+}
+
+/* the result lines of one query, formatted by up to 16 threads into pieces that are then written in order */
+typedef struct {
+  const int32_t *ids;
+  const float *m;
+  char *const *names;
+  uint64_t lo, hi;
+  int l2;
+  char *buf;
+  size_t len;
+} abv_fmt_job;
+
+static void *abv_fmt_run(void *p) {
+  abv_fmt_job *j = p;
+  size_t cap = (size_t)(j->hi - j->lo) * 48 + 64;
+  j->buf = malloc(cap);
+  j->len = 0;
+  for (uint64_t i = j->lo; i < j->hi && j->buf; i++) {
+    const char *nm = j->names[j->ids[i]];
+    const double v = j->l2 ? sqrt((double)j->m[i]) : (double)j->m[i]; /* :319 prints sqrt of the L2 sum */
+    for (;;) {
+      const int w = snprintf(j->buf + j->len, cap - j->len, "%s\t%lf\n", nm, v);
+      if (w >= 0 && (size_t)w < cap - j->len) { j->len += (size_t)w; break; }
+      cap = cap * 2 + (size_t)(w > 0 ? w : 64);
+      char *nb = realloc(j->buf, cap);
+      if (!nb) { free(j->buf); j->buf = NULL; break; }
+      j->buf = nb;
+    }
+  }
+  return NULL;
+}
+
+static void abv_print(const int32_t *ids, const float *m, uint64_t cnt, char *const *names, int l2) {
+  abv_fmt_job jobs[16];
+  int nt = (int)(cnt / 4096);
+  if (nt < 1) nt = 1;
+  if (nt > 16) nt = 16;
+  pthread_t th[16];
+  for (int t = 0; t < nt; t++) {
+    jobs[t] = (abv_fmt_job){ids, m, names, cnt * (uint64_t)t / (uint64_t)nt, cnt * (uint64_t)(t + 1) / (uint64_t)nt, l2, NULL, 0};
+    if (t && pthread_create(&th[t], NULL, abv_fmt_run, &jobs[t]) != 0) die("abv_search(): pthread_create");
+  }
+  abv_fmt_run(&jobs[0]);
+  for (int t = 0; t < nt; t++) {
+    if (t) pthread_join(th[t], NULL);
+    if (!jobs[t].buf) die("abv_search(): out of memory");
+    fwrite(jobs[t].buf, 1, jobs[t].len, stdout);
+    free(jobs[t].buf);
+  }
+}
+
+static int composite_search(const char *refdir, int metric, int nargs, char **args, int device) {
+  char path[PATHLEN * 3 + 64];
+  double t_read = 0, t_kernel = 0, t_fmt = 0, t0 = now_s();
+  /* :218-252: names (fgets of PATHLEN, newline cut), norms, cumulative counts, matrix */
+  size_t nn = 0, yn = 0, in = 0, mn = 0;
+  snprintf(path, sizeof path, "%s/abundance_Vec.name", refdir);
+  char *nb = (char *)read_whole(path, &nn);
+  if (!nb) die("abv_search():%s", path);
+  nb[nn] = 0;
+  /* fgets(PATHLEN) pieces: up to PATHLEN - 1 bytes or through the newline; the name is the piece up to its newline */
+  size_t ncap = 1024, S = 0, ol = 0;
+  char **names = malloc(sizeof(char *) * ncap), *ob = malloc(2 * nn + 1);
+  if (!names || !ob) die("abv_search(): out of memory");
+  for (size_t pos = 0; pos < nn;) {
+    size_t take = 0;
+    while (take < PATHLEN - 1 && pos + take < nn) { if (nb[pos + take++] == '\n') break; }
+    if (S == ncap) { ncap *= 2; names = realloc(names, sizeof(char *) * ncap); if (!names) die("abv_search(): out of memory"); }
+    size_t l = strcspn(nb + pos, "\n");
+    if (l > take) l = take;
+    memcpy(ob + ol, nb + pos, l);
+    ob[ol + l] = 0;
+    names[S++] = ob + ol;
+    ol += l + 1;
+    pos += take;
+  }
+  if (S > 0xFFFFFFFFull) die("abv_search(): too many samples");
+  snprintf(path, sizeof path, "%s/abundance_Vec.yl2n", refdir);
+  double *yl2n = (double *)read_whole(path, &yn);
+  if (!yl2n || yn < 8 * S) die("abv_search():%s", path);
+  snprintf(path, sizeof path, "%s/abundance_Vec.abmi", refdir);
+  int32_t *abmi = (int32_t *)read_whole(path, &in);
+  if (!abmi) die("abv_search():%s", path);
+  snprintf(path, sizeof path, "%s/abundance_Vec.abm", refdir);
+  mk_binvec *abm = (mk_binvec *)read_whole(path, &mn);
+  if (!abm) die("abv_search():%s", path);
+  t_read += now_s() - t0;
+  mk_abv *a = NULL; /* made (and the index loaded) at the first vector: arguments that are all skipped need no device */
+  static const char *head[3] = {"CosineXY", "L1norm", "L2norm"};
+  uint32_t batch = 64;
+  if (S && (uint64_t)batch * S > 0xFFFFFFFFull) batch = (uint32_t)(0xFFFFFFFFull / S);
+  if (batch < 1) batch = 1;
+  int *qarg = malloc(sizeof(int) * (size_t)(nargs > 0 ? nargs : 1));
+  uint64_t *qend = malloc(8 * (size_t)batch), *oend = malloc(8 * (size_t)batch);
+  size_t qcap = 1 << 12;
+  mk_binvec *qv = malloc(sizeof(mk_binvec) * qcap);
+  for (int i = 0; i < nargs;) {
+    /* a batch: arguments i .. j-1, of which nq are vectors; a file that cannot be read ends the batch before it */
+    uint32_t nq = 0;
+    uint64_t nd = 0;
+    int j = i, fail = -1;
+    t0 = now_s();
+    for (; j < nargs && nq < batch; j++) {
+      if (!abv_name_ok(args[j])) continue;
+      if (strchr(args[j], '/')) snprintf(path, sizeof path, "%s", args[j]); /* :245-247 */
+      else snprintf(path, sizeof path, "%s/abundance_Vec/%s", refdir, args[j]);
+      FILE *f = fopen(path, "rb");
+      struct stat fs;
+      if (!f || fstat(fileno(f), &fs) != 0) { if (f) fclose(f); fail = j; break; }
+      const uint64_t len = (uint64_t)fs.st_size / sizeof(mk_binvec);
+      if (nd + len > qcap) { while (nd + len > qcap) qcap *= 2; qv = realloc(qv, sizeof(mk_binvec) * qcap); if (!qv) die("abv_search(): out of memory"); }
+      if (len && fread(qv + nd, sizeof(mk_binvec), len, f) != len) { fclose(f); fail = j; break; }
+      fclose(f);
+      nd += len;
+      qarg[nq] = j;
+      qend[nq++] = nd;
+    }
+    t_read += now_s() - t0;
+    const int32_t *ids = NULL;
+    const float *ms = NULL;
+    int64_t bad = -1;
+    t0 = now_s();
+    if (nq && !a) {
+      if (mk_abv_create(device, &a) != MK_OK) die("mk_abv_create failed: %s", mk_abv_last_error(NULL));
+      if (mk_abv_load(a, abm, mn / sizeof(mk_binvec), abmi, (uint32_t)(in / 4), yl2n, (uint32_t)S) != MK_OK)
+        die("abv_search(): %s/abundance_Vec: %s", refdir, mk_abv_last_error(a));
+    }
+    if (nq && mk_abv_search(a, metric, nq, qv, qend, oend, &ids, &ms, &bad) != MK_OK) {
+      if (bad >= 0) { /* the queries before the bad one are printed first, as the reference would have */
+        nq = (uint32_t)bad;
+        fail = -2;
+        j = qarg[bad];
+        if (nq && mk_abv_search(a, metric, nq, qv, qend, oend, &ids, &ms, NULL) != MK_OK) die("abv_search(): %s", mk_abv_last_error(a));
+      } else die("abv_search(): %s", mk_abv_last_error(a));
+    }
+    t_kernel += now_s() - t0;
+    t0 = now_s();
+    uint32_t k = 0;
+    for (; i < j; i++) {
+      if (!abv_name_ok(args[i])) { printf("%dth argument %s is not a .abv file, skipped\n", i, args[i]); continue; }
+      const uint64_t lo = k ? oend[k - 1] : 0, hi = oend[k];
+      printf("#Sample\t%s\n", head[metric]);
+      abv_print(ids + lo, ms + lo, hi - lo, names, metric == 2);
+      k++;
+    }
+    t_fmt += now_s() - t0;
+    if (fail == -2) {
+      const char *p = args[j];
+      die("abv_search(): %s: species outside the index", p);
+    }
+    if (fail >= 0) die("abv_search():%s: %s", path, strerror(errno ? errno : EIO));
+  }
+  if (a) mk_abv_destroy(a);
+  fflush(stdout);
+  if (getenv("MK_ABV_TIMES")) /* tools/bench_abv.py: where the command's wall time goes */
+    fprintf(stderr, "{\"read_s\": %.6f, \"device_s\": %.6f, \"format_s\": %.6f}\n", t_read, t_kernel, t_fmt);
+  free(qarg); free(qend); free(oend); free(qv); free(names); free(ob); free(nb); free(abm); free(abmi); free(yl2n);
+  return 0;
+}
+
 static int cmd_composite(int argc, char **argv) {
   const char *refdir = NULL, *qrydir = NULL, *outdir = "./";
   int binvec = 0, device = 0;
@@ -1337,14 +1577,31 @@ static int cmd_composite(int argc, char **argv) {
         return composite_read_abv(nf, files) == 1 ? 0 : 1;
       }
     }
+  int index = 0, metric = -1, npos = 0;
+  char **pos = NULL;
   for (int i = 0; i < argc; i++) {
     if (!strcmp(argv[i], "-r") && i + 1 < argc) refdir = argv[++i];
     else if (!strcmp(argv[i], "-q") && i + 1 < argc) qrydir = argv[++i];
     else if (!strcmp(argv[i], "-o") && i + 1 < argc) outdir = argv[++i];
     else if (!strcmp(argv[i], "-p") && i + 1 < argc) ++i;
     else if (!strcmp(argv[i], "-b")) binvec = 1;
+    else if (!strcmp(argv[i], "-i")) index = 1;
+    else if (!strcmp(argv[i], "-s") && i + 1 < argc) metric = atoi(argv[++i]); /* :83: atoi, as argp hands it over */
+    else if (!strncmp(argv[i], "-s", 2) && argv[i][2] && argv[i][2] != '-') metric = atoi(argv[i] + 2); /* -s1, the README's form */
     else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
-    else die("composite option %s is not part of this build (-r -q -b -o and -d are)", argv[i]);
+    else if (argv[i][0] != '-') { pos = argv + i; npos = argc - i; break; } /* ARGP_KEY_ARGS: the rest are the query vectors */
+    else die("composite option %s is not part of this build (-r -q -i -s -b -o and -d are)", argv[i]);
+  }
+  /* cmd_composite() :170-178: -q, else -i, else -s, else the usage line */
+  if (refdir && !qrydir) {
+    if (index) return composite_index(refdir, device);
+    if (metric != -1) {
+      if (metric >= 0 && metric < 3 && npos > 0) return composite_search(refdir, metric, npos, pos, device);
+      printf("\vUsage: metakssd composite -r <ref> -s <0|1|2> <query.abv>\n\v");
+      return 0;
+    }
+    printf("\vUsage: metakssd composite -r <ref> < mode: -q | -i | -s >\n\v");
+    return 0;
   }
   if (!refdir || !qrydir || !strcmp(refdir, qrydir)) die("get_species_abundance(): refdir or qrydir is not initialized");
   char path[PATHLEN * 3 + 64];
