@@ -14,7 +14,11 @@ Workloads (BASELINE.json configs):
   --total-reads T       config 4's table regime at any N (N = 1: 80 GB of rows on one GPU).
 
 Rank 0 prints ONE JSON line (contract in the task statement): `value` is the HBM-resident whole-job rate; `roofline`
-is the scan kernel (HIP-event timed inside the engine on its launch stream); at N = 1 also
+is the scan kernel (HIP-event timed inside the engine on its launch stream).  A plain run does only that: set up, warm up,
+time the steps, write --dump-outputs, print the line.  Everything else it can measure or check runs with --full (each side
+leg can still be left out there with its --no-... flag); at N = 1 --full adds
+  `split_queues`  the split-queue flow timed beside the headline for the same passes (--split-cus),
+  `roofline.traffic` from two rocprofv3 --pmc child runs, `roofline.measured_copy_gb_s` a device-to-device copy,
   `cpu_baseline`  the compiled reference (oracle/_ref/metakssd, kind "reference") or the oracle port on this host's cores
                   over a bounded sample of the same workload,
   `t_stream`      the same reads from PINNED HOST rows through mk_sketch_push_reads (H2D double-buffered) to the result,
@@ -24,6 +28,9 @@ is the scan kernel (HIP-event timed inside the engine on its launch stream); at 
                   Neither host-inclusive rate is `value`.
   `config5`       BASELINE config 5 through the product command line: a directory of synthetic genomes as multi-FASTA files,
                   no -A, L3K10 and L2K11 (genomes/s and Gbases/s by the parent's clock; --no-config5 skips it).
+  `next_rows`     composite, stage II and dist -r through the command line, and their kernels (--no-next-rows skips it).
+and at N > 1 --full adds `rank0_tail_*` (three separately fenced steps), `t_stream`, `inproc_multi` and `same_workload_one_gpu`
+(the last two can also be asked for one by one: --inproc-multi, --one-gpu-reference).
 
 --dump-outputs DIR writes the sketch of the LAST timed step -- what a caller of the library receives -- as .npy files under DIR
 (dump_outputs()), so that two builds run with the same arguments (the same seeded reads) can be compared output for output.
@@ -1145,11 +1152,14 @@ def main():
     ap.add_argument("--reads-per-gpu", type=int, default=None, help="weak scaling: this many reads on every rank")
     ap.add_argument("--total-reads", type=int, default=None,
                     help="strong scaling: this many reads split over the ranks (default with N > 1: 500 M = BASELINE config 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every side leg as well (CPU baseline, host-inclusive and command-line legs, split-queue flow, counter passes, "
+                         "N > 1: rank 0's tail, the libmetakssd_multi.so and one-GPU legs); without it the run does only what the headline needs")
     ap.add_argument("--cpu-sample-reads", type=int, default=4_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-legs", action="store_true", help="skip t_stream / t_e2e / config5 (N = 1 only anyway)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-host-legs", action="store_true", help="with --full: skip t_stream / t_e2e / config5 / next_rows / traffic")
     ap.add_argument("--split-cus", type=int, default=32,
-                    help="N = 1: the SIDE leg `split_queues` -- two engines take the passes in turn, the scan kernel on all but this many compute "
+                    help="N = 1, with --full: the SIDE leg `split_queues` -- two engines take the passes in turn, the scan kernel on all but this many compute "
                          "units and what follows a scan on these (MK_OPT_SPLIT_CUS; a multiple of 32); 0: no side leg.  The headline is always "
                          "one engine on one queue")
     ap.add_argument("--no-tail-hint", action="store_true", help="experiment: the last pass of a split-queue run does not say that nothing follows it")
@@ -1178,13 +1188,13 @@ def main():
                     help="N > 1: how the ranks' partial sketches are merged.  gather: every list to rank 0, one import there.  slices: "
                          "SURVEY.md 8e's alternative -- all-to-all by key %% N, every rank folds a key slice, the reduced slices are rank 0's "
                          "key list.  auto (default): gather below four ranks, slices from four on (what libmetakssd_multi.so does)")
-    ap.add_argument("--inproc-multi", action=argparse.BooleanOptionalAction, default=True,
-                    help="N > 1 (on by default; --no-inproc-multi skips it): after the timed region rank 0 ALSO drives the C product's own "
+    ap.add_argument("--inproc-multi", action=argparse.BooleanOptionalAction, default=None,
+                    help="N > 1 (on with --full; --no-inproc-multi skips it): after the timed region rank 0 ALSO drives the C product's own "
                          "multi-GPU path in its process -- libmetakssd_multi.so on devices 0..N-1 (mk_multi_create, one engine per GPU, RCCL "
                          "group send/recv, mk_multi_finish: what `metakssd dist --devices` runs) -- on the same workload while the other ranks "
                          "wait off the GPU; reported as `inproc_multi`")
-    ap.add_argument("--one-gpu-reference", action=argparse.BooleanOptionalAction, default=True,
-                    help="N > 1 (on by default): after the timed region rank 0 sketches the WHOLE workload alone on its GPU (the N = 1 point of "
+    ap.add_argument("--one-gpu-reference", action=argparse.BooleanOptionalAction, default=None,
+                    help="N > 1 (on with --full): after the timed region rank 0 sketches the WHOLE workload alone on its GPU (the N = 1 point of "
                          "the same curve: --gpus 1 --total-reads T gives the same figure as a line of its own) -> `same_workload_one_gpu` with "
                          "speedup and efficiency")
     ap.add_argument("--verify", action="store_true",
@@ -1196,6 +1206,11 @@ def main():
                     help="(internal) run ONLY the libmetakssd_multi.so leg on this comma-separated device list and print its JSON: rank 0 of an N > 1 run "
                          "starts this as a child process so that an RCCL that hangs or dies there cannot take the bench line with it")
     args = ap.parse_args()
+    if args.inproc_multi is None:
+        args.inproc_multi = args.full
+    if args.one_gpu_reference is None:
+        args.one_gpu_reference = args.full
+    host_legs = args.full and not args.no_host_legs
     if args.steps is None:
         args.steps = 300 if args.gpus == 1 else 40
     if args.steps < 1:
@@ -1232,7 +1247,7 @@ def main():
     # now and then much slower (0.2 instead of 0.055 s), beside a parent that holds one (
     # profiles/r05_e2e_parent_state.txt).  Their sketches are compared with the resident passes' further down.
     early = {}
-    if world == 1 and not args.no_host_legs and args.total_reads is None:
+    if world == 1 and host_legs and args.total_reads is None:
         n_cli = args.reads_per_gpu if args.reads_per_gpu is not None else CONFIG3_READS
         wait_device_quiet(least=0.0, most=15.0)  # whatever ran on the device before this process may still be handing its memory back
         try:
@@ -1426,7 +1441,7 @@ def main():
     # pass i run BESIDE the scan of pass i + 1 -- on one queue they cannot (the two kernels do not fit on one CU
     # together).  Every pass is still a whole sketch, begin to result in host memory, all of it inside the timed region; the host calls are
     # ordered so that the next scan is queued before the wait inside mk_sketch_finish_begin.
-    split = args.split_cus if world == 1 and not args.serial_finish else 0
+    split = args.split_cus if world == 1 and not args.serial_finish and (args.full or args.split_leg_only) else 0
     eng_cus = torch.cuda.get_device_properties(dev).multi_processor_count
     split_note = None
     engs = None
@@ -1525,7 +1540,7 @@ def main():
 
     # The HEADLINE flow is fixed before anything is timed: one engine, one queue, every kernel on the whole device -- what every caller of
     # the library gets.  The split-queue flow (two engines in turn, MK_OPT_SPLIT_CUS) stays an option of the library and is timed BESIDE the
-    # headline for the same passes and the same warm-up (`split_queues` in the line), never instead of it: over the driver's 20 passes it
+    # headline under --full for the same passes and the same warm-up (`split_queues` in the line), never instead of it: over the driver's 20 passes it
     # won by 0-3 % on some boxes and lost on others (profiles/r05_f_bench_driver_steps20*.json), which is not a rule to pick a headline by.
     one_queue = split_queues = trial = None
     split_timed = 0  # compute units the TIMED flow leaves to a second queue: 0 except under --split-leg-only
@@ -1552,7 +1567,7 @@ def main():
         except capi.MkError as ex:
             split_note = "split queues not available here (%s)" % str(ex)[:160]
 
-    if world > 1:  # rank 0's serial tail (gather + import + finish), from three separately fenced steps
+    if world > 1 and args.full:  # rank 0's serial tail (gather + import + finish), from three separately fenced steps
         tail["on"] = True
         for _ in range(3):
             step()
@@ -1563,7 +1578,7 @@ def main():
     # buffer over ITS PCIe link (mk_sketch_push_reads), then the same export / gather / import / finish.  At most 50 M reads per
     # rank are pinned (8 GB): with fewer ranks than that allows the leg runs on the first 50 M reads of each rank's range.
     stream_n = None
-    if world > 1 and not args.no_host_legs:
+    if world > 1 and host_legs:
         ns = min(n, 50_000_000)
         pinned = torch.empty(ns * STRIDE, dtype=torch.uint8, pin_memory=True)
         pinned.copy_(reads[:ns * STRIDE])
@@ -1581,7 +1596,7 @@ def main():
         del pinned
 
     verified = None
-    need_sketch = args.verify or (world == 1 and not args.no_host_legs) or (world > 1 and (args.inproc_multi or args.one_gpu_reference))
+    need_sketch = args.verify or (world == 1 and host_legs) or (world > 1 and (args.inproc_multi or args.one_gpu_reference))
     if need_sketch:
         flags["keep"] = True
         step()
@@ -1697,7 +1712,7 @@ def main():
         scan_ms = prof["scan_ms"] / launches
         achieved = scan_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
         traffic, traffic_source = None, None
-        if world == 1 and not args.no_host_legs and not args.no_traffic and total_reads == CONFIG3_READS:
+        if world == 1 and host_legs and not args.no_traffic and total_reads == CONFIG3_READS:
             traffic, traffic_source = leg_traffic(int(reads_per_launch))
         tfile = os.path.join(ROOT, "profiles", "scan_traffic.json")
         if traffic is None and os.path.exists(tfile):
@@ -1715,7 +1730,7 @@ def main():
                 traffic = None
         # a measured ceiling beside the nominal 8 TB/s: device-to-device copy of 2 GiB of the rows, read + write bytes
         copy_gbs = None
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 nb = min(int(reads.numel()), 2 << 30)
                 dst = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -1797,12 +1812,12 @@ def main():
             line["dump_outputs"] = dump_outputs(args.dump_outputs, result.pop("dump"))
         if args.backend != "nccl":
             line["config"]["parallelism"] += " (debug transport: %s%s)" % (args.backend, ", same device" if args.same_device else "")
-        if world == 1 and not args.no_host_legs:
+        if world == 1 and host_legs:
             try:
                 line["t_stream"] = leg_stream(torch, capi, eng, reads, n)
             except Exception as ex:
                 line["t_stream"] = {"gbases_s": None, "what": "failed: %s" % ex}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             m = min(args.cpu_sample_reads, n)
             eng.begin(capi.MK_MODE_KOC)
             eng.push_reads_device(reads.data_ptr(), STRIDE, m, 0)
@@ -1812,7 +1827,7 @@ def main():
             except Exception as ex:  # a missing zcat etc. must not lose the GPU number
                 line["cpu_baseline"] = {"value": None, "unit": "Gbases/s", "cores": os.cpu_count(), "kind": "reference",
                                         "sample": "failed: %s" % ex}
-        if world == 1 and not args.no_host_legs:
+        if world == 1 and host_legs:
             sketch = result["sketch"]
             del reads
             eng.close()  # the command line brings its own engine: give the memory back first
@@ -1833,7 +1848,7 @@ def main():
                     line["t_e2e"].pop("_sketch", None)
                 except Exception as ex:
                     line["t_e2e"] = {"gbases_s": None, "what": "failed: %s" % ex}
-        if world == 1 and not args.no_host_legs and not args.no_config5:
+        if world == 1 and host_legs and not args.no_config5:
             if "config5" in early:
                 line["config5"] = early["config5"]
             else:
@@ -1841,7 +1856,7 @@ def main():
                     line["config5"] = leg_config5(capi)
                 except Exception as ex:
                     line["config5"] = {"what": "failed: %s" % ex}
-        if world == 1 and not args.no_host_legs and not args.no_next_rows:
+        if world == 1 and host_legs and not args.no_next_rows:
             nr = early.get("next_rows", {})
             try:
                 nr["kernels"] = leg_next_rows_kernels(capi, local_rank)

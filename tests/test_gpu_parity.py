@@ -1067,7 +1067,7 @@ def test_bench_two_rank_flow_merged_equals_single(capi):
     port = ui.free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device",
-           "--reads-per-gpu", "1000000", "--steps", "1", "--warmup", "1", "--verify"]  # (the N > 1 t_stream leg runs too)
+           "--reads-per-gpu", "1000000", "--steps", "1", "--warmup", "1", "--verify", "--full"]  # (the N > 1 t_stream leg runs too)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -1110,7 +1110,7 @@ def test_bench_launches_its_own_ranks(capi, ranks, merge):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--reads-per-gpu", "600000", "--steps", "2", "--warmup", "1",
-           "--no-host-legs", "--verify", "--inproc-multi", "--merge", merge]
+           "--no-host-legs", "--verify", "--inproc-multi", "--merge", merge, "--full"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200, env=env)
     assert r.returncode == 0, "\n".join(l for l in r.stderr.decode(errors="replace").splitlines() if "Error" in l or "error" in l or "rank0" in l)[-4000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -1126,7 +1126,7 @@ def test_bench_launches_its_own_ranks(capi, ranks, merge):
 
 
 def test_bench_default_flow_one_gpu(capi):
-    """`python3 bench.py` at N = 1 as the driver starts it (device legs only, a small workload): the headline is ALWAYS one engine on one
+    """`python3 bench.py --full` at N = 1 (device legs only, a small workload): the headline is ALWAYS one engine on one
     queue -- fixed before anything is timed, not the faster of two flows -- and the split-queue flow (MK_OPT_SPLIT_CUS) is a side leg timed
     for the same passes and warm-up; a setting the option does not fit, or 0, leaves the headline alone"""
     import json
@@ -1135,7 +1135,7 @@ def test_bench_default_flow_one_gpu(capi):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    base = [sys.executable, os.path.join(root, "bench.py"), "--reads-per-gpu", "2000000", "--steps", "7", "--warmup", "2", "--no-host-legs",
+    base = [sys.executable, os.path.join(root, "bench.py"), "--reads-per-gpu", "2000000", "--steps", "7", "--warmup", "2", "--full", "--no-host-legs",
             "--no-cpu-baseline", "--no-traffic", "--verify"]
     lines = []
     for extra in (["--no-split-leg"], ["--split-cus", "24"], ["--split-cus", "0"], []):
@@ -1158,9 +1158,32 @@ def test_bench_default_flow_one_gpu(capi):
     assert d["config"]["distinct_keys"] == bad["config"]["distinct_keys"] == one["config"]["distinct_keys"] == auto["config"]["distinct_keys"] > 0
 
 
+def test_bench_plain_run_is_headline_only(capi, tmp_path):
+    """`python3 bench.py` without --full at N = 1 (a small workload): the headline and the dump of the last timed step, and none of the
+    side legs that --full adds"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--reads-per-gpu", "2000000", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
+    d = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Gbases/s"
+    assert d["config"]["queues"].startswith("one engine, one queue") and d["config"]["distinct_keys"] > 0
+    for leg in ("split_queues", "queue_flows", "split_queues_note", "cpu_baseline", "t_stream", "t_e2e", "config5", "next_rows"):
+        assert leg not in d, leg
+    assert d["roofline"]["measured_copy_gb_s"] is None
+    assert d["dump_outputs"]["distinct_keys"] == d["config"]["distinct_keys"]
+    assert np.load(os.path.join(out, "sketch_c0_ids.npy")).size == d["config"]["distinct_keys"]
+
+
 def test_bench_bare_two_ranks_is_interpretable(capi):
-    """`python3 bench.py --gpus 2`, nothing else (on this one-GPU box the ranks share GPU 0 over gloo, and the line says so): BASELINE config 4
-    split over the ranks, and with NO flag the line carries what a scaling curve needs -- the C product's own multi-GPU library timed
+    """`python3 bench.py --gpus 2 --full`, nothing else (on this one-GPU box the ranks share GPU 0 over gloo, and the line says so): BASELINE config 4
+    split over the ranks, and with no other flag the line carries what a scaling curve needs -- the C product's own multi-GPU library timed
     (`inproc_multi`, with its transport), the same workload on one GPU in the same run (`same_workload_one_gpu`: ms, speedup, efficiency),
     every rank seen"""
     import json
@@ -1169,7 +1192,7 @@ def test_bench_bare_two_ranks_is_interpretable(capi):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500, env=env)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500, env=env)
     assert r.returncode == 0, "\n".join(l for l in r.stderr.decode(errors="replace").splitlines() if "rror" in l or "rank0" in l)[-4000:]
     d = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["total_reads"] == 500_000_000 and d["steps"] == 40

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05_multi_one_gpu.jsonl; : > $O
 for total in 50000000 500000000; do
   for merge in gather slices; do
-    python3 bench.py --gpus 8 --total-reads $total --steps 5 --warmup 1 --no-host-legs --merge $merge --verify --inproc-multi 2> gpurun_out/multi_${total}_$merge.err | grep '^{' >> $O
+    python3 bench.py --gpus 8 --total-reads $total --steps 5 --warmup 1 --full --no-host-legs --merge $merge --verify --inproc-multi 2> $(dirname $O)/multi_${total}_$merge.err | grep '^{' >> $O
     tail -1 $O | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
