@@ -8,11 +8,20 @@ do not need the CPU oracle (which would take minutes at this size):
   * counts: every id once, every count >= 1, the number of distinct keys bench.py reports for this workload, the sum of
     counts within 5 sigma of the expected number of accepted k-mers (129 per read x 1/4096)
 
-The same engine is checked against the oracle bit for bit at oracle-sized inputs in test_gpu_parity.py."""
+  * the bytes: the first sketch equals what the COMPILED REFERENCE wrote at -p 1 for the same reads (entries `config3` and `config4`
+    of tests/golden/fullsize_digests.json, made by tests/golden/make_golden_fullsize.py: sha256 of combco.0, of combco.0.a, of
+    both, and of the sorted (id, count) multiset).  Everything above compares the engine with itself; this compares it with the
+    reference, at the size and table load the project is measured at.
+
+The same engine is checked against the oracle bit for bit at oracle-sized inputs in test_gpu_parity.py, and against the reference's
+digests on smaller prefixes of this stream, a dense table and every row geometry in test_gpu_refdigest.py (the config-4 test
+below skips without 104 GB of free HBM; the dense-table test there needs 5)."""
 import ctypes as C
 
 import numpy as np
 import pytest
+
+import fullsize_ref as fr
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +64,7 @@ def test_full_size_sketch_properties(capi, shufs, reads_dev):
     e0, e1 = capi.Engine(shuf, 0), capi.Engine(shuf, 0)
     try:
         ids, cnt = sketch(capi, e0, reads_dev, 1)
+        fr.assert_equals_reference(fr.entries()["config3"], ids, cnt, "device rows, pitch 160, one push")
         ids2, cnt2 = sketch(capi, e0, reads_dev, 1)
         assert np.array_equal(ids, ids2) and np.array_equal(cnt, cnt2)            # deterministic
         ids7, cnt7 = sketch(capi, e0, reads_dev, 7)
@@ -135,6 +145,7 @@ def test_config4_regime_whole_equals_eight_shards(capi, shufs):
         assert ids.size == np.unique(ids).size and cnt.min() >= 1, msg
         total_occ = int(cnt.astype(np.int64).sum())
         assert abs(total_occ - N4 * 129 / 4096) < 5 * (N4 * 129 / 4096) ** 0.5, msg
+        fr.assert_equals_reference(fr.entries()["config4"], ids, cnt, "device rows, pitch 160, eight pushes")
 
         # eight contiguous shards: shard 0 stays in e0's table, 1..7 are sketched on e1 one after the other, exported and
         # imported into e0 (what GPU 0 does with the lists of GPUs 1..7)

@@ -9,7 +9,8 @@ on the GPU, and the two sketch directories are compared as sorted (id, count) mu
 insertion order -- and with it the byte order of its files -- is not reproducible, the keys and their counts are.
 The reference's check-then-write insert (iseq2comem.c:701-718) is racy under OpenMP: keys it LOSES or DOUBLES at this size are
 reported, not hidden (`reference_only` / `product_only` / `count_differs`); `reference_p1_sample` adds an exact byte comparison
-on a sample the reference finishes at -p 1.
+on a sample the reference finishes at -p 1.  The byte comparison at FULL size needs no run of this tool: tests/golden/fullsize_digests.json holds
+the sha256 of the reference's -p 1 files for both configs (tests/golden/make_golden_fullsize.py), and tests/test_gpu_fullsize.py compares with them.
 
     python tools/check_fullsize_vs_ref.py [--reads 50000000] [--p1-sample 2000000] [--out profiles/r04_fullsize_vs_reference.json]
 Needs a GPU, oracle/_ref/metakssd and about 2.1 x reads x 320 bytes of /dev/shm."""
