@@ -33,6 +33,8 @@
  *   mco_cbdco_nobin_dist() counting loop             command_dist.c:1033-1049        mk_mco_count_begin/add/finish
  *   index_abv() species-major matrix                 command_composite.c:347-440     mk_abv_index
  *   abv_search() accumulation + qsort                command_composite.c:212-344     mk_abv_load / mk_abv_search
+ *   reads2mco() per-record id streams                iseq2comem.c:88-214             mk_byread_begin/push_text/take/finish
+ *   core_reverse2unituple() + one fprintf per k-mer  command_reverse.c:206-220,342-368 mk_reverse_ids
  *   dist_print_nobin() / output_ctrl()               command_dist.c:1531-1690        mk_dist_print
  *
  * Conventions: plain pointers and sizes only; every function returns MK_OK (0) or a negative
@@ -634,6 +636,46 @@ int mk_abv_search(mk_abv *a, int metric, uint32_t nq, const mk_binvec *q, const 
                   const int32_t **samples, const float **measures, int64_t *bad_query);
 /* measurement: device time of the last index's and the last search's kernels, from HIP events on the handle's stream */
 int mk_abv_last_kernel_ms(mk_abv *a, double *index_ms, double *search_ms);
+
+/* ---- `dist --byread` and `reverse`: per-record id streams and k-mer recovery ---------------------------------------------
+ * reads2mco() (iseq2comem.c:88-214) appends, for every accepted window of the file in text order, the id drtuple >> comp_code_bits
+ * to combco.<drtuple % component_num> -- repeats and key 0 kept, no hashlimit -- and writes per component the cumulative id
+ * counts over the records (record n = what lies between the n-th '>' and the next; record 0 = what precedes the first '>').
+ * The byte walk is fasta2co()'s (mk_sketch_push_stream).  co_reverse2kmer() / co_rvs2kmer_byreads() (command_reverse.c:148-353)
+ * turn ids back into canonical k-mers.  Both run on the device; no CPU path: mk_byread_create fails with MK_ERR_NO_DEVICE
+ * without a HIP device.  Device memory of a handle does not grow with the file. */
+#define MK_BYREAD_MAX_PUSH (8u << 20) /* bytes of text per mk_byread_push_text */
+typedef struct mk_byread mk_byread;
+int mk_byread_create(int device, mk_byread **out);
+int mk_byread_destroy(mk_byread *b);
+const char *mk_byread_last_error(const mk_byread *b); /* b may be NULL: last error of a failed create */
+/* seq2co_global_var_initial() (iseq2comem.c:54-86) and the open of the output files (:93-106): a new file.  p->shuf_table must
+ * stay valid until the handle is destroyed or begun again.  Also loads rev_shuf_arr (command_reverse.c:150-160) for
+ * mk_reverse_ids. */
+int mk_byread_begin(mk_byread *b, const mk_params *p);
+/* the byte loop (iseq2comem.c:127-200) over the next n <= MK_BYREAD_MAX_PUSH bytes of the file; window, header state, record
+ * number and the components' counts carry over from push to push, so the cuts may fall anywhere.  final != 0 with the file's
+ * last bytes (n may be 0).  MK_ERR_FORMAT: the file ends inside a '>' line (the reference gives up there, :161-170). */
+int mk_byread_push_text(mk_byread *b, const void *text, uint64_t n, int final);
+/* what the last push added for one component: the ids to append to combco.<c> (fwrite, iseq2comem.c:197-198) and the entries
+ * to append to combco.index.<c> (the cumulative loop, :202-207) -- one per record that was completed by this push, the last
+ * record with the final push.  The arrays are the handle's (pinned) and stay valid until the next push. */
+int mk_byread_take(mk_byread *b, uint32_t component, const uint32_t **ids, uint64_t *n_ids, const uint64_t **index, uint64_t *n_index);
+/* behind the final push: readn (iseq2comem.c:159), the ids of all components, the kernels' time in ms (HIP events); each may be NULL */
+int mk_byread_finish(mk_byread *b, uint64_t *records, uint64_t *total_ids, double *kernel_ms);
+/* core_reverse2unituple() (command_reverse.c:355-368) and the letter loop + fprintf (:214-219, :342-348) for n ids of one
+ * component: out_text receives n lines of 2k letters and a '\n' (n * (2k + 1) bytes, no terminator).  Needs a begun handle (the
+ * parameters and the table are those of mk_byread_begin).  MK_ERR_FORMAT: the table does not have exactly 4096 entries
+ * below 4096 (:160). */
+int mk_reverse_ids(mk_byread *b, const uint32_t *ids, uint64_t n, uint32_t component, char *out_text);
+/* the cofiles.stat of a by-read directory (command_dist.c:477-500): infile_num 1, all_ctx_ct 0, the ctx_ct word 0 (the
+ * reference leaves it uninitialised), input_path in PATHLEN bytes.  MK_ERR_ARG: a path of 256 bytes or more. */
+int mk_byread_write_stat(const char *outdir, const mk_params *p, const char *input_path);
+/* the file name co_reverse2kmer() writes a sketch's k-mers to (command_reverse.c:335-337): basename of the recorded path (a
+ * PATHLEN field of cofiles.stat), ' ' -> '_' */
+int mk_reverse_outname(const char *recorded_path, char *out, size_t cap);
+/* kernels of the pushes since mk_byread_begin / of the mk_reverse_ids calls since then, in ms */
+int mk_byread_last_kernel_ms(mk_byread *b, double *emit_ms, double *reverse_ms);
 
 /* distance.out (host).  Options as command_dist_wrapper.c:83-92. */
 typedef struct mk_dist_opts {

@@ -196,6 +196,16 @@ def _load():
         "mk_abv_load": [vp, vp, u64, vp, u32, vp, u32],
         "mk_abv_search": [vp, C.c_int, u32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)],
         "mk_abv_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+        "mk_byread_create": [C.c_int, C.POINTER(vp)],
+        "mk_byread_destroy": [vp],
+        "mk_byread_begin": [vp, C.POINTER(ParamsC)],
+        "mk_byread_push_text": [vp, vp, u64, C.c_int],
+        "mk_byread_take": [vp, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64)],
+        "mk_byread_finish": [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double)],
+        "mk_reverse_ids": [vp, vp, u64, u32, vp],
+        "mk_byread_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+        "mk_byread_write_stat": [C.c_char_p, C.POINTER(ParamsC), C.c_char_p],
+        "mk_reverse_outname": [C.c_char_p, C.c_char_p, C.c_size_t],
         "mk_dist_print": [vp, C.POINTER(DistOptsC), i32, i32, u32, u32, vp, vp, vp, vp, vp],
         "mk_sketchdir_open": [C.c_char_p, C.POINTER(ParamsC), C.c_int, C.c_int, C.POINTER(vp)],
         "mk_sketchdir_add": [vp, C.c_char_p, C.POINTER(ResultC)],
@@ -213,6 +223,8 @@ def _load():
     lib.mk_mco_last_error.restype = C.c_char_p
     lib.mk_abv_last_error.argtypes = [vp]
     lib.mk_abv_last_error.restype = C.c_char_p
+    lib.mk_byread_last_error.argtypes = [vp]
+    lib.mk_byread_last_error.restype = C.c_char_p
     lib.mk_setop_stream.argtypes = [vp]
     lib.mk_setop_stream.restype = vp
     lib.mk_last_error.argtypes = [vp]
@@ -1057,6 +1069,94 @@ class Abv:
         if self.h:
             lib.mk_abv_destroy(self.h)
             self.h = C.c_void_p()
+
+
+MK_BYREAD_MAX_PUSH = 8 << 20
+
+
+class ByRead:
+    """`dist --byread` and `reverse` on the device (mk_byread_*: reads2mco(), iseq2comem.c:88-214; command_reverse.c:148-368)"""
+
+    def __init__(self, shuf, device=0, component_sz=8):
+        self.h = C.c_void_p()
+        rc = lib.mk_byread_create(device, C.byref(self.h))
+        if rc:
+            raise MkError(rc, (lib.mk_byread_last_error(None) or b"").decode())
+        self.shuf = shuf  # the table must outlive the handle
+        self.params = shuf.params(component_sz)
+        self.begin()
+
+    def _check(self, rc):
+        if rc:
+            raise MkError(rc, (lib.mk_byread_last_error(self.h) or b"").decode())
+
+    def begin(self):
+        self._check(lib.mk_byread_begin(self.h, C.byref(self.params)))
+        C_ = self.params.component_num
+        self._ids = [[] for _ in range(C_)]
+        self._index = [[] for _ in range(C_)]
+
+    def push_text(self, text, final=False):
+        """the next bytes of the file (at most MK_BYREAD_MAX_PUSH); what the push added is taken and kept for finish()"""
+        buf = np.frombuffer(bytes(text), dtype=np.uint8)
+        self._check(lib.mk_byread_push_text(self.h, buf.ctypes.data if buf.size else None, buf.size, 1 if final else 0))
+        for c in range(self.params.component_num):
+            ids, idx, nid, nix = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+            self._check(lib.mk_byread_take(self.h, c, C.byref(ids), C.byref(nid), C.byref(idx), C.byref(nix)))
+            if nid.value:
+                self._ids[c].append(np.frombuffer((C.c_char * (4 * nid.value)).from_address(ids.value), dtype=np.uint32).copy())
+            if nix.value:
+                self._index[c].append(np.frombuffer((C.c_char * (8 * nix.value)).from_address(idx.value), dtype=np.uint64).copy())
+
+    def finish(self):
+        """-> (ids per component uint32, index per component uint64 [records + 1], records, kernel ms)"""
+        rec, tot, ms = C.c_uint64(0), C.c_uint64(0), C.c_double(0.0)
+        self._check(lib.mk_byread_finish(self.h, C.byref(rec), C.byref(tot), C.byref(ms)))
+        ids = [np.concatenate(x) if x else np.zeros(0, np.uint32) for x in self._ids]
+        index = [np.concatenate(x) if x else np.zeros(0, np.uint64) for x in self._index]
+        assert sum(len(i) for i in ids) == tot.value
+        return ids, index, rec.value, ms.value
+
+    def run(self, text, pieces=None):
+        """a whole text: begin, pushes of `pieces` bytes each (default MK_BYREAD_MAX_PUSH; a list gives the cut points), finish"""
+        self.begin()
+        text = bytes(text)
+        if isinstance(pieces, (list, tuple)):
+            cuts = [0] + list(pieces) + [len(text)]
+        else:
+            step = pieces or MK_BYREAD_MAX_PUSH
+            cuts = list(range(0, len(text), step)) + [len(text)]
+            if len(cuts) == 1:
+                cuts = [0, 0]
+        for i in range(len(cuts) - 1):
+            self.push_text(text[cuts[i]:cuts[i + 1]], final=i == len(cuts) - 2)
+        return self.finish()
+
+    def reverse_ids(self, ids, component):
+        """the text `reverse` prints for these ids of one component: lines of 2k letters + newline, as bytes"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        out = np.empty(ids.size * (self.params.TL + 1), np.uint8)
+        self._check(lib.mk_reverse_ids(self.h, ids.ctypes.data if ids.size else None, ids.size, component, out.ctypes.data if out.size else None))
+        return out.tobytes()
+
+    def last_kernel_ms(self):
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self._check(lib.mk_byread_last_kernel_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if self.h:
+            lib.mk_byread_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def reverse_ids(shuf, ids, component, device=0):
+    """one-shot form of ByRead.reverse_ids"""
+    b = ByRead(shuf, device)
+    try:
+        return b.reverse_ids(ids, component)
+    finally:
+        b.close()
 
 
 def dist_print(path, ref_ctx_ct, qry_ctx_ct, refnames, qrynames, ct, kmerlen, dim_rd_len, metric=0, outfields=2, correction=0,

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "host/mk_host_internal.h"
+#include "mk_key.hip.h" /* mk_keyparams, mk_reduce_key, mk_revcomp, mk_accept_key, the wave helpers */
 
 #define MK_WAVE 64
 #define MK_MAX_CB 128                  /* widest column block staged per step, bytes */
@@ -30,13 +31,6 @@
 #define MK_CNT_BITS 24                 /* slot word = key << 24 | count (the reference's slot is key << 16 | count16) */
 #define MK_CNT_MASK 0xFFFFFFull
 #define MK_CNT_SAT 0xF00000ull         /* stop adding long before the count field could carry into the key */
-
-struct mk_keyparams {
-  uint64_t tupmask, domask, undomask, lowmask;
-  uint32_t TL, crvsaddmove, out2 /*2*half_outctx_len*/, key_lshift /*2*TL-4*out*/, dr4 /*4*drlevel*/;
-  int32_t dim_start, dim_end;
-  uint32_t S; /* hashsize */
-};
 
 struct mk_table {
   unsigned long long *kc;     /* key << 24 | occurrences (>= 1), 0 = empty   [S]  (keys are < 2^39) */
@@ -114,18 +108,6 @@ struct mk_scan_args {
 };
 
 /* ------------------------------------------------------------------------------------------------ */
-__device__ __forceinline__ uint32_t mk_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t mk_mbcnt(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-__device__ __forceinline__ void mk_wave_lds_fence() {
-  /* same-wave LDS producer -> consumer: DS operations of one wave execute in order; this only stops
-   * the compiler from moving LDS accesses across the hand-off */
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 /* probe step of HASH(K,I,S) = (K%S + I*(1+K%(S-1))) % S, incrementally: n_{i+1} = (n_i + h2) mod S */
 __device__ __forceinline__ void mk_probe_init(uint64_t key, uint32_t S, uint32_t &n, uint32_t &h2) {
   n = (uint32_t)(key % S);
@@ -134,11 +116,6 @@ __device__ __forceinline__ void mk_probe_init(uint64_t key, uint32_t S, uint32_t
 __device__ __forceinline__ uint32_t mk_probe_next(uint32_t n, uint32_t h2, uint32_t S) {
   uint64_t t = (uint64_t)n + h2;
   return (uint32_t)(t >= S ? t - S : t);
-}
-
-/* key reduction: iseq2comem.c:696-699 */
-__device__ __forceinline__ uint64_t mk_reduce_key(const mk_keyparams &kp, uint64_t uni, uint64_t pf) {
-  return (((uni & kp.undomask) + ((uni & kp.lowmask) << kp.key_lshift)) >> kp.dr4) + pf;
 }
 
 /* counted upsert into the accumulation table (arrival order is irrelevant: counts add, first ordinals
@@ -222,16 +199,6 @@ __device__ __forceinline__ bool mk_front_open(const mk_table &tab) {
   return tab.fr && __hip_atomic_load(&tab.fr->state[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u;
 }
 
-/* reverse complement of a k-mer of `TL` bases held in the low 2*TL bits: reverse the 2-bit groups of the
- * complement.  Equals the reference's incrementally built crvstuple (iseq2comem.c:686). */
-__device__ __forceinline__ uint64_t mk_revcomp(uint64_t f, uint32_t TL) {
-  uint64_t n = ~f;
-  n = ((n >> 2) & 0x3333333333333333ull) | ((n & 0x3333333333333333ull) << 2);
-  n = ((n >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((n & 0x0F0F0F0F0F0F0F0Full) << 4);
-  n = __builtin_bswap64(n);
-  return n >> (64u - 2u * TL);
-}
-
 /* The scan kernel's 2-bit code of a base is (byte >> 1) & 3: A=0 C=1 T=2 G=3 -- two VALU ops per four bases
  * cheaper than the reference's A=0 C=1 G=2 T=3 (Basemap, global_basic.c:62-69).  The two codings differ by the
  * Gray map c ^ (c >> 1), which is its own inverse on 2 bits; the LDS filter is built over re-coded substrings
@@ -245,13 +212,9 @@ __device__ __forceinline__ void mk_resolve_one(const mk_scan_args &a, uint64_t s
   const uint64_t fwd = mk_scan_to_ref_codes(scan_fwd);
   const uint64_t rc = mk_revcomp(fwd, a.kp.TL);
   const uint64_t uni = fwd < rc ? fwd : rc;
-  const uint32_t dim = (uint32_t)((uni & a.kp.domask) >> a.kp.out2);
-  /* most candidates are filter false positives or wrong-strand mirrors: settle those on the small bitmap and
-   * touch the 4*16^subk-byte .shuf table only for the accepted ones */
-  if (!((a.accept_bits[dim >> 5] >> (dim & 31u)) & 1u)) return;
-  const int32_t pf = a.shuf[dim];
-  if (pf >= a.kp.dim_start && pf < a.kp.dim_end) {
-    const uint64_t key = mk_reduce_key(a.kp, uni, (uint64_t)(pf - a.kp.dim_start));
+  /* most candidates are filter false positives or wrong-strand mirrors: mk_accept_key settles those on the small bitmap */
+  uint64_t key;
+  if (mk_accept_key(a.kp, a.accept_bits, a.shuf, uni, key)) {
     if (a.batch) mk_b_upsert(*a.batch, (uint32_t)(ord >> 12), key, ord);
     else mk_upsert_big(a.tab, a.kp.S, key, ord, 1u); /* (overflow path of the scan kernel only: straight to the big table) */
   }
