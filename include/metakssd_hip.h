@@ -677,6 +677,87 @@ int mk_reverse_outname(const char *recorded_path, char *out, size_t cap);
 /* kernels of the pushes since mk_byread_begin / of the mk_reverse_ids calls since then, in ms */
 int mk_byread_last_kernel_ms(mk_byread *b, double *emit_ms, double *reverse_ms);
 
+/* ---- BGZF-compressed FASTQ inflated on the device (the -A reader; replaces the `zcat -fc` pipe of iseq2comem.c:666-669 for
+ * files `bgzip` wrote) ------------------------------------------------------------------------------------------------------
+ * A BGZF file is a chain of independent gzip members of at most 64 KiB of text; any zcat reads it as multi-member gzip, so the
+ * reference accepts these files and its output is the parity target.
+ *   mk_bgzf_scan          host: is the WHOLE file such a chain?  If so, one table entry per member
+ *   mk_inflate_blocks     device: one wavefront inflates one member (stored, fixed and dynamic blocks) and checks its CRC32
+ *   mk_fastq_frame_device device: mk_fastq_frame's rule (four lines a record, the sequence line with its '\n' is the row) on text in HBM
+ *   mk_sketch_push_bgzf   the three bound to an engine: compressed bytes cross PCIe, rows go to mk_sketch_push_reads_device
+ * There is no CPU path for the device parts: mk_inflate_create fails with MK_ERR_NO_DEVICE without a HIP device. */
+typedef struct mk_bgzf_block {
+  uint64_t in_off;  /* where the member starts in the file */
+  uint64_t out_off; /* where its text starts in the inflated file: the sum of the ISIZEs in front of it */
+  uint32_t in_len;  /* BSIZE + 1 */
+  uint32_t pay_off, pay_len; /* the deflate stream, relative to in_off */
+  uint32_t crc32, isize;     /* the trailer */
+  uint32_t reserved;
+} mk_bgzf_block;
+/* The file is `size` bytes at `mem`, or (mem == NULL) behind the descriptor fd.  *is_bgzf = 1 and a table (free it with
+ * mk_bgzf_free) when every byte of the file belongs to a member that starts with 1f 8b 08, has FLG == FEXTRA exactly, an extra
+ * field with one 'B','C' subfield of SLEN 2 whose BSIZE keeps the member inside the file, and ISIZE <= 65536; empty members are
+ * legal wherever they occur.  Anything else -- a plain gzip member, trailing bytes, a member cut off by the end of the file, an
+ * empty file -- is *is_bgzf = 0 with MK_OK: not an error, the caller takes the zcat route.  Host code only. */
+int mk_bgzf_scan(int fd, const uint8_t *mem, size_t size, mk_bgzf_block **blocks, uint64_t *nblocks, uint64_t *total_out, int *is_bgzf);
+void mk_bgzf_free(mk_bgzf_block *blocks);
+/* what the inflate kernel leaves per member */
+enum {
+  MK_INFL_OK = 0,
+  MK_INFL_BAD_BLOCK = 1,    /* deflate block type 3, or a stored block whose LEN and NLEN disagree */
+  MK_INFL_BAD_LENGTHS = 2,  /* code length header: counts out of range, a repeat without a predecessor or past the end, no end-of-block code */
+  MK_INFL_BAD_CODE = 3,     /* over-subscribed or incomplete code, or a bit pattern / symbol no code assigns */
+  MK_INFL_BAD_DISTANCE = 4, /* distance beyond the start of the member's output */
+  MK_INFL_INPUT = 5,        /* the deflate stream needs more bytes than the member holds */
+  MK_INFL_OUTPUT_LEN = 6,   /* the stream gives more or fewer bytes than ISIZE */
+  MK_INFL_CRC = 7           /* the text's CRC32 is not the trailer's */
+};
+const char *mk_inflate_status_text(int status);
+typedef struct mk_inflate mk_inflate;
+int mk_inflate_create(int device, mk_inflate **out);
+int mk_inflate_destroy(mk_inflate *h);
+const char *mk_inflate_last_error(const mk_inflate *h); /* h may be NULL: last error of a failed create */
+/* `comp` (host) holds the members of blocks[0..nblocks): in_off is relative to `comp`, out_off to the output.  The bytes are
+ * staged through pinned memory, every member is inflated to its out_off in HBM and its status lands in status[] (host, one per
+ * member; a damaged member is a status, never a fault: the kernel reads nothing outside a member's payload and writes nothing
+ * outside its ISIZE bytes).  out_host != NULL: the text is copied back (out_cap >= the end of the last member's text).  The
+ * call returns MK_OK whatever the statuses are. */
+int mk_inflate_blocks(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_bgzf_block *blocks, uint64_t nblocks,
+                      uint8_t *out_host, size_t out_cap, uint32_t *status);
+/* mk_fastq_frame on the device: `text` (host, n < 2^30 bytes, starting at a record boundary) is copied to HBM and framed there;
+ * *stride = MK_ROW_PITCH(longest sequence line incl. its '\n' among the rows), the rows are copied back to rows_host when it is
+ * not NULL (MK_ERR_ARG when rows_cap is too small for *nrows * *stride bytes); *consumed = the end of the last complete record,
+ * or n when final; *longest = the longest line of any kind.  MK_ERR_FORMAT: a line of 4095 characters or more. */
+int mk_fastq_frame_device(mk_inflate *h, const uint8_t *text, size_t n, int final, uint8_t *rows_host, size_t rows_cap,
+                          uint32_t *stride, uint64_t *nrows, size_t *consumed, uint32_t *longest);
+/* kernels of the last mk_inflate_blocks / mk_fastq_frame_device, in ms (HIP events on the handle's stream) */
+int mk_inflate_last_kernel_ms(mk_inflate *h, double *inflate_ms, double *frame_ms);
+
+typedef struct mk_bgzf_opts {
+  uint64_t chunk_bytes; /* text bytes per chunk = one upload, one inflate launch, one framing pass; 0 = 128 MiB, at least one member */
+  uint64_t reserved;
+} mk_bgzf_opts;
+typedef struct mk_bgzf_stats {
+  uint64_t blocks, chunks, comp_bytes, text_bytes, rows;
+  double inflate_ms, frame_ms; /* device time of the inflate (with CRC) and of the framing kernels */
+  double t_scan_s, t_read_s, t_total_s; /* host: the walk, reading the file into pinned staging, the whole call */
+  int64_t bad_block;   /* MK_ERR_FORMAT from a damaged member: its index in the file; -1 otherwise */
+  int32_t bad_status;  /* ... and its MK_INFL_* status */
+  int32_t reserved;
+} mk_bgzf_stats;
+/* The first `size` bytes behind fd, a BGZF file (MK_ERR_ARG when mk_bgzf_scan says it is not), go into the sketch begun on e:
+ * per chunk the compressed bytes and the table slice cross PCIe through pinned staging, the members are inflated and checked,
+ * the text is framed (what lies behind a chunk's last complete record is carried in front of the next chunk's text) and the rows
+ * are scanned with consecutive ordinals from first_ordinal on; two chunks are in flight.  Rows and errors are those of
+ * mk_fastq_frame over the inflated text with final != 0.  MK_ERR_FORMAT: a damaged member (st->bad_block >= 0; no further row is
+ * pushed, the sketch must be abandoned) or a line of 4095+ characters (st->bad_block == -1).  Engines with MK_OPT_SPLIT_CUS:
+ * MK_ERR_STATE.  Returns when the device is done with the file. */
+int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, uint64_t first_ordinal, mk_bgzf_stats *st);
+const char *mk_bgzf_last_error(void); /* text of the calling thread's last failed mk_sketch_push_bgzf */
+/* the stream the engine's kernels are queued on now and its device, for work that must be ordered with them (staged rows are
+ * flushed first).  MK_ERR_STATE with MK_OPT_SPLIT_CUS (two queues: no single stream orders with the scan). */
+int mk_engine_get_stream(mk_engine *e, void **hip_stream, int *device);
+
 /* distance.out (host).  Options as command_dist_wrapper.c:83-92. */
 typedef struct mk_dist_opts {
   int32_t metric;     /* -M: 0 Jaccard / MashD, 1 containment / AafD */

@@ -100,6 +100,21 @@ class DistOptsC(C.Structure):
                 ("dthreshold", C.c_double)]
 
 
+class BgzfBlockC(C.Structure):
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("pay_off", C.c_uint32), ("pay_len", C.c_uint32),
+                ("crc32", C.c_uint32), ("isize", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BgzfOptsC(C.Structure):
+    _fields_ = [("chunk_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class BgzfStatsC(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("chunks", C.c_uint64), ("comp_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("rows", C.c_uint64),
+                ("inflate_ms", C.c_double), ("frame_ms", C.c_double), ("t_scan_s", C.c_double), ("t_read_s", C.c_double), ("t_total_s", C.c_double),
+                ("bad_block", C.c_int64), ("bad_status", C.c_int32), ("reserved", C.c_int32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -210,6 +225,13 @@ def _load():
         "mk_sketchdir_open": [C.c_char_p, C.POINTER(ParamsC), C.c_int, C.c_int, C.POINTER(vp)],
         "mk_sketchdir_add": [vp, C.c_char_p, C.POINTER(ResultC)],
         "mk_sketchdir_close": [vp],
+        "mk_bgzf_scan": [C.c_int, vp, C.c_size_t, C.POINTER(C.POINTER(BgzfBlockC)), C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int)],
+        "mk_inflate_create": [C.c_int, C.POINTER(vp)],
+        "mk_inflate_destroy": [vp],
+        "mk_inflate_blocks": [vp, vp, C.c_size_t, C.POINTER(BgzfBlockC), u64, vp, C.c_size_t, vp],
+        "mk_fastq_frame_device": [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_size_t), C.POINTER(u32)],
+        "mk_inflate_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+        "mk_sketch_push_bgzf": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), u64, C.POINTER(BgzfStatsC)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -225,6 +247,14 @@ def _load():
     lib.mk_abv_last_error.restype = C.c_char_p
     lib.mk_byread_last_error.argtypes = [vp]
     lib.mk_byread_last_error.restype = C.c_char_p
+    lib.mk_inflate_last_error.argtypes = [vp]
+    lib.mk_inflate_last_error.restype = C.c_char_p
+    lib.mk_inflate_status_text.argtypes = [C.c_int]
+    lib.mk_inflate_status_text.restype = C.c_char_p
+    lib.mk_bgzf_last_error.argtypes = []
+    lib.mk_bgzf_last_error.restype = C.c_char_p
+    lib.mk_bgzf_free.argtypes = [C.POINTER(BgzfBlockC)]
+    lib.mk_bgzf_free.restype = None
     lib.mk_setop_stream.argtypes = [vp]
     lib.mk_setop_stream.restype = vp
     lib.mk_last_error.argtypes = [vp]
@@ -479,6 +509,21 @@ class Engine:
     def begin_occ(self, min_occurrence=1):
         """FASTQ without -A (fastq2co): ids of keys seen at least min_occurrence times"""
         _check(lib.mk_sketch_begin_occ(self.h, min_occurrence), self.h)
+
+    def push_bgzf(self, path, chunk_bytes=0, first_ordinal=0):
+        """a BGZF-compressed FASTQ file into the sketch in progress (mk_sketch_push_bgzf) -> BgzfStatsC; a damaged member or a
+        long line raises MkError(MK_ERR_FORMAT) with the statistics in .stats"""
+        o, st = BgzfOptsC(chunk_bytes, 0), BgzfStatsC()
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            rc = lib.mk_sketch_push_bgzf(self.h, fd, os.fstat(fd).st_size, C.byref(o), first_ordinal, C.byref(st))
+        finally:
+            os.close(fd)
+        if rc:
+            err = MkError(rc, (lib.mk_bgzf_last_error() or b"").decode())
+            err.stats = st
+            raise err
+        return st
 
     def push_reads(self, rows, stride, first_read_ordinal=0):
         """rows: host numpy u8 array of nreads*stride bytes (stride | MK_ROWS_PACKED: 64-byte packed rows)"""
@@ -1072,6 +1117,85 @@ class Abv:
 
 
 MK_BYREAD_MAX_PUSH = 8 << 20
+
+
+MK_INFL_OK, MK_INFL_BAD_BLOCK, MK_INFL_BAD_LENGTHS, MK_INFL_BAD_CODE, MK_INFL_BAD_DISTANCE, MK_INFL_INPUT, MK_INFL_OUTPUT_LEN, MK_INFL_CRC = range(8)
+BGZF_FIELDS = ("in_off", "out_off", "in_len", "pay_off", "pay_len", "crc32", "isize")
+
+
+def bgzf_scan(data=None, path=None):
+    """mk_bgzf_scan over bytes or over a file: None when the input is not BGZF from its first byte to its last, else a list of
+    dicts (BGZF_FIELDS), one per member.  Host code: no GPU needed."""
+    tab, nb, total, is_b = C.POINTER(BgzfBlockC)(), C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+    if path is not None:
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            _check(lib.mk_bgzf_scan(fd, None, os.fstat(fd).st_size, C.byref(tab), C.byref(nb), C.byref(total), C.byref(is_b)))
+        finally:
+            os.close(fd)
+    else:
+        b = np.frombuffer(bytes(data), dtype=np.uint8)
+        _check(lib.mk_bgzf_scan(-1, b.ctypes.data if len(b) else C.c_void_p(1), len(b), C.byref(tab), C.byref(nb), C.byref(total), C.byref(is_b)))
+    if not is_b.value:
+        return None
+    out = [{f: int(getattr(tab[i], f)) for f in BGZF_FIELDS} for i in range(nb.value)]
+    assert total.value == sum(x["isize"] for x in out)
+    lib.mk_bgzf_free(tab)
+    return out
+
+
+class Inflate:
+    """BGZF members inflated and FASTQ text framed on the device (mk_inflate_*), with copies back to the host for tests"""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        rc = lib.mk_inflate_create(device, C.byref(self.h))
+        if rc:
+            raise MkError(rc, (lib.mk_inflate_last_error(None) or b"").decode())
+
+    def _check(self, rc):
+        if rc:
+            raise MkError(rc, (lib.mk_inflate_last_error(self.h) or b"").decode())
+
+    def blocks(self, comp, table):
+        """comp: the file's bytes, table: bgzf_scan's entries (or hand-made ones) -> (text bytes, status per member)"""
+        b = np.frombuffer(bytes(comp), dtype=np.uint8)
+        n = len(table)
+        arr = (BgzfBlockC * max(1, n))()
+        for i, t in enumerate(table):
+            for f in BGZF_FIELDS:
+                setattr(arr[i], f, t[f])
+        end = max([t["out_off"] + t["isize"] for t in table] + [0])
+        out = np.zeros(max(1, end), dtype=np.uint8)
+        st = np.full(max(1, n), 0xFFFFFFFF, dtype=np.uint32)
+        self._check(lib.mk_inflate_blocks(self.h, b.ctypes.data, len(b), arr, n, out.ctypes.data, end, st.ctypes.data))
+        return out[:end].tobytes(), [int(x) for x in st[:n]]
+
+    def frame(self, text, final=True):
+        """mk_fastq_frame_device -> (rows u8 [nrows * stride], stride, nrows, consumed, longest line, rc)"""
+        b = np.frombuffer(bytes(text), dtype=np.uint8)
+        cap = (len(b) // 4 + 1) * 4096 if len(b) < (1 << 16) else len(b) * 4 + 4096
+        rows = np.zeros(cap, dtype=np.uint8)
+        stride, nrows, used, longest = C.c_uint32(0), C.c_uint64(0), C.c_size_t(0), C.c_uint32(0)
+        rc = lib.mk_fastq_frame_device(self.h, b.ctypes.data if len(b) else None, len(b), 1 if final else 0, rows.ctypes.data, cap,
+                                       C.byref(stride), C.byref(nrows), C.byref(used), C.byref(longest))
+        return rows[: nrows.value * stride.value], stride.value, nrows.value, used.value, longest.value, rc
+
+    def kernel_ms(self):
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self._check(lib.mk_inflate_last_kernel_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if self.h:
+            lib.mk_inflate_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ByRead:

@@ -150,6 +150,9 @@ static int g_mmap_input = 0;  /* --mmap-input: the FASTQ file is mapped and the 
 static int g_early_chunks = 96; /* --early-chunks: chunks of a FASTQ file framed before the engine is there (mk_fastq_opts::early_chunks) */
 static int g_frame_early = 0; /* --frame-early: every chunk of a FASTQ file may be framed at once, also while the runtime and the engine come up (measurement) */
 static int g_ahead = MK_DEFAULT_AHEAD; /* --ahead: row buffers the FASTQ stream's framers may run ahead of the pushes by */
+static int g_no_device_inflate = 0; /* --no-device-inflate: BGZF inputs through `zcat -fc` like every other .gz (measurement) */
+static uint64_t g_inflate_chunk_bytes = 0; /* --inflate-chunk-kib: text bytes per chunk of the device route (test hook; 0 = the library's default) */
+static int g_timing = 0; /* --timing */
 static int g_component_sz = 8; /* --component-sz: the reference's compile-time COMPONENT_SZ (global_basic.h:35-37) */
 
 /* libmetakssd_multi.so (it links librccl.so, 570 MB) is loaded only when --devices names several GPUs */
@@ -201,6 +204,7 @@ typedef struct {
   uint8_t *arena; /* row-buffer pool of the FASTQ stream: an anonymous mapping, pinned piece by piece behind the framers (pin_*) */
   size_t arena_bytes;
   struct pinner *pin;
+  int bgzf_ok; /* one engine on one GPU: a BGZF-compressed FASTQ on the -A reader is inflated on the device (sketch_fastq_bgzf) */
 } ctx_t;
 
 #define CHECK(e, call)                                                  \
@@ -608,8 +612,53 @@ static int sketch_fastq_mapped(ctx_t *c, const char *path) {
   return 1;
 }
 
+/* --timing: which way a compressed FASTQ went, one JSON line per input */
+static void report_route(const char *path, const char *route, const mk_bgzf_stats *bs) {
+  if (!g_timing) return;
+  printf("{\"input\": \"%s\", \"route\": \"%s\", \"blocks\": %llu, \"chunks\": %llu, \"comp_bytes\": %llu, \"text_bytes\": %llu, \"rows\": %llu, "
+         "\"inflate_ms\": %.3f, \"frame_ms\": %.3f, \"bgzf_scan_s\": %.4f, \"read_s\": %.4f, \"route_total_s\": %.4f}\n",
+         path, route, bs ? (unsigned long long)bs->blocks : 0ull, bs ? (unsigned long long)bs->chunks : 0ull, bs ? (unsigned long long)bs->comp_bytes : 0ull,
+         bs ? (unsigned long long)bs->text_bytes : 0ull, bs ? (unsigned long long)bs->rows : 0ull, bs ? bs->inflate_ms : 0.0, bs ? bs->frame_ms : 0.0,
+         bs ? bs->t_scan_s : 0.0, bs ? bs->t_read_s : 0.0, bs ? bs->t_total_s : 0.0);
+}
+
+/* a .gz that is a BGZF chain from its first byte to its last (mk_bgzf_scan) is inflated, checked and framed on the device; 0: not
+ * such a file, the caller goes on with `zcat -fc`, with today's behaviour and messages */
+static int sketch_fastq_bgzf(ctx_t *c, const char *path) {
+  if (!c->bgzf_ok || c->occ || g_no_device_inflate || !has_suffix(path, ".gz")) return 0;
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return 0;
+  struct stat st;
+  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size == 0) { close(fd); return 0; }
+  mk_bgzf_block *tab = NULL;
+  uint64_t nb = 0, total = 0;
+  int is_bgzf = 0;
+  if (mk_bgzf_scan(fd, NULL, (size_t)st.st_size, &tab, &nb, &total, &is_bgzf) != MK_OK || !is_bgzf) { close(fd); return 0; }
+  mk_bgzf_free(tab);
+  mk_engine *e = sketch_engine(c);
+  if (c->t_first_push == 0) c->t_first_push = now_s() - g_t0;
+  mk_bgzf_opts o;
+  memset(&o, 0, sizeof o);
+  o.chunk_bytes = g_inflate_chunk_bytes;
+  mk_bgzf_stats bs;
+  const int rc = mk_sketch_push_bgzf(e, fd, (size_t)st.st_size, &o, c->next_ordinal, &bs);
+  close(fd);
+  if (rc == MK_ERR_FORMAT && bs.bad_block >= 0)
+    die("%s: BGZF block %lld is damaged (%s): the input was not read completely", path, (long long)bs.bad_block, mk_inflate_status_text(bs.bad_status));
+  if (rc == MK_ERR_FORMAT)
+    die("%s: FASTQ line longer than the reference's fgets() width (%s): outside the framing contract", path, "4094 characters, iseq2comem.c:656,673");
+  if (rc != MK_OK) die("mk_sketch_push_bgzf failed (%d): %s", rc, mk_bgzf_last_error());
+  c->next_ordinal += bs.rows;
+  c->nrows_total += bs.rows;
+  c->t_last_push = now_s() - g_t0;
+  report_route(path, "device-inflate", &bs);
+  return 1;
+}
+
 static void sketch_fastq(ctx_t *c, const char *path) {
   if (sketch_fastq_mapped(c, path)) return;
+  if (sketch_fastq_bgzf(c, path)) return;
+  if (is_compressed(path)) report_route(path, "zcat", NULL);
   ensure_buffers(c);
   input_t in;
   if (!open_input(path, &in)) die("mtfastq2koc():%s: %s", path, strerror(errno));
@@ -2605,7 +2654,9 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--host-fasta")) g_host_fasta = 1; /* FASTA windows made on the host (mk_fasta_window), not on the device */
     else if (!strcmp(argv[i], "--quiet")) quiet = 1;
     else if (!strcmp(argv[i], "--component-sz") && i + 1 < argc) g_component_sz = atoi(argv[++i]);
-    else if (!strcmp(argv[i], "--timing")) timing = 1;
+    else if (!strcmp(argv[i], "--timing")) timing = g_timing = 1;
+    else if (!strcmp(argv[i], "--no-device-inflate")) g_no_device_inflate = 1;
+    else if (!strcmp(argv[i], "--inflate-chunk-kib") && i + 1 < argc) g_inflate_chunk_bytes = (uint64_t)atoll(argv[++i]) << 10;
     else if (!strcmp(argv[i], "--chunk-mib") && i + 1 < argc) chunk_bytes = (uint64_t)atoi(argv[++i]) << 20;
     else if (!strcmp(argv[i], "--inflight") && i + 1 < argc) inflight = atoi(argv[++i]); /* row buffers queued for copying */
     else if (!strcmp(argv[i], "--frame-early")) g_frame_early = 1;
@@ -2738,6 +2789,7 @@ int main(int argc, char **argv) {
   c.inflight = inflight;
   c.direct_host = direct_host;
   c.packed = !ascii_rows && mk_params_packed_ok(&P);
+  c.bgzf_ok = ndev <= 1 && n_engines == 1 && !shard_files;
   /* packed rows are 64 bytes a read on PCIe instead of 160: the framers, not the link, bound a FASTQ file then, and 32 of them did
    * better than 24 (50 M reads: 0.20-0.24 s against 0.22-0.26 from process start; 48 and more are slower again) */
   if (c.packed && !threads_given && ncpu >= 32) nthreads = 32;

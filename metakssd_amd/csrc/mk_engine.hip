@@ -839,6 +839,17 @@ extern "C" int mk_engine_sync(mk_engine *e) {
   return MK_OK;
 }
 
+extern "C" int mk_engine_get_stream(mk_engine *e, void **hip_stream, int *device) {
+  if (!e || !hip_stream) return MK_ERR_ARG;
+  if (e->scan_stream) return mk_fail(e, MK_ERR_STATE, "mk_engine_get_stream: MK_OPT_SPLIT_CUS runs the scan on a queue of its own");
+  MK_HIP(e, hipSetDevice(e->device));
+  { int rc = mk_flush_region(e); if (rc) return rc; }
+  if (e->copy_stream != e->stream) MK_HIP(e, hipStreamSynchronize(e->copy_stream)); /* (staged rows: their scan is queued, their copies are done) */
+  *hip_stream = (void *)e->stream;
+  if (device) *device = e->device;
+  return MK_OK;
+}
+
 extern "C" int mk_profile_enable(mk_engine *e, int on) { if (!e) return MK_ERR_ARG; e->profiling = on != 0; return MK_OK; }
 
 extern "C" int mk_profile_reset(mk_engine *e) {

@@ -1,0 +1,968 @@
+/*
+ * mk_inflate.hip -- BGZF-compressed FASTQ on the device (gfx950, wave64, hand-written): inflate, CRC32, FASTQ framing.
+ *
+ * The reference reads a compressed input through one `zcat -fc` child (iseq2comem.c:666-669): one CPU core running inflate bounds
+ * the whole path.  A BGZF file (`bgzip`) is a chain of independent gzip members of at most 64 KiB of text, each with its compressed
+ * size in its header and its text size in its trailer (host/mk_bgzf.c walks them), so only the compressed bytes cross PCIe and:
+ *
+ *   mk_inflate_kernel    one WAVEFRONT per member, four to a workgroup.  Symbol decoding is serial per member and is done
+ *                        wave-uniformly: every lane holds the same bit buffer and takes the same branches, table look-ups are LDS
+ *                        broadcasts.  The compressed bytes pass through a 1 KiB window per wave in LDS, refilled by all 64 lanes (one
+ *                        16-byte load each).  Code tables are built in LDS per deflate block: lane l counts and places the symbols of
+ *                        length l (a canonical code is sorted by length, then symbol) and fills their entries of a 10-bit (literal /
+ *                        length) or 8-bit (distance) look-up table; longer codes take the canonical bit-by-bit walk.  Literals collect
+ *                        in one register (lane i holds the i-th pending literal) and leave as one store; a match is copied by all
+ *                        lanes, out[pos + i] = out[pos - dist + i mod dist], which is what a byte-serial copy gives for dist < len.  A
+ *                        match whose source was written since the wave last waited for its stores waits first.  Then the text's
+ *                        CRC32: every lane runs the byte table over an equal slice (the text is thought padded with zero bytes IN
+ *                        FRONT, which a zero register ignores; the all-ones start value is the first four bytes complemented), and
+ *                        the 64 registers are folded with the 32x32 GF(2) matrix "advance by one slice", squared at every level.
+ *                        Safety: loads stay inside the member's payload rounded to 16 bytes, stores inside the ISIZE bytes at the
+ *                        member's offset, every loop consumes input bits or produces output bytes and is bounded by the two sizes;
+ *                        malformed data ends the member with a status (MK_INFL_*), written with an ordinary store.
+ *   mk_fq_count_kernel   newlines per 4 KiB tile of the text and the last one's place
+ *   mk_fq_scan_kernel    one workgroup: exclusive prefix over the tiles (= the line number at every tile's start), the number of
+ *                        complete records, the first member with a bad status
+ *   mk_fq_reduce_kernel  a wave per tile, a lane per 64 bytes: every newline's line number and the newline in front of it (from the
+ *                        lanes' bit masks; from the text in front of the tile only for the tile's first) -> the longest line, the
+ *                        longest sequence line of a complete record, the end of the last complete record
+ *   mk_fq_rows_kernel    the same walk; the sequence lines found are copied by the whole wave, four bytes a lane, zero-padded
+ *   mk_fq_carry_kernel   what lies behind the last complete record moves in front of the next chunk's text
+ * The framing rule is mk_fastq_frame_range's (host/mk_frontend.c) and depends on line numbers only: record r is lines 4r..4r+3, it
+ * gives a row iff its fourth line has at least one byte, the row is line 4r+1 with its '\n'.  (One difference, outside the contract
+ * either way: a line of 4095+ characters is refused wherever it stands, also in a last record that lacks lines.)
+ * Bound of each kernel: DESIGN.md 4.10.
+ */
+#include <hip/hip_runtime.h>
+#include "mk_poison.hip.h"
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+#include <time.h>
+#include <unistd.h>
+
+#include "metakssd_hip.h"
+
+#define MK_INFL_WAVES 4u
+#define MK_INFL_WIN 1024u      /* bytes of the compressed stream a wave holds in LDS */
+#define MK_INFL_LBITS 10u
+#define MK_INFL_DBITS 8u
+#define MK_FQ_TILE 4096u       /* text bytes per wave */
+#define MK_FQ_WAVES 4u
+#define MK_FQ_CARRY 16384u     /* room in front of a chunk's text: four lines of at most 4095 bytes (more means a line that long) */
+#define MK_FQ_LINE_MAX 4096u   /* MK_FQ_LEN: a line of this many bytes with its '\n' is refused (mk_frontend.c) */
+
+namespace {
+
+struct mk_infl_blk { uint32_t pay_off, pay_len, out_off, isize, crc; };
+
+struct mk_fq_res {
+  uint32_t nl, nrec, consumed, maxline, maxseq; /* text coordinates */
+  uint32_t bad_block, bad_status;               /* first member with a status != 0 (0xffffffff: none) */
+  uint32_t pad;
+};
+
+__device__ __forceinline__ void mk_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+/* the wave's stores to global memory are done before anything that follows is issued */
+__device__ __forceinline__ void mk_store_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+__device__ __forceinline__ uint32_t mk_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+__device__ const uint16_t mk_lbase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+__device__ const uint8_t mk_lext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+__device__ const uint16_t mk_dbase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+__device__ const uint8_t mk_dext[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+__device__ const uint8_t mk_clorder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+struct mk_infl_lds { /* one wave's */
+  uint32_t win[MK_INFL_WIN / 4];
+  uint16_t lit_tab[1u << MK_INFL_LBITS];
+  uint16_t dist_tab[1u << MK_INFL_DBITS];
+  uint16_t lit_sym[288], dist_sym[32];
+  uint16_t lit_cnt[16], dist_cnt[16];
+  uint8_t lens[352]; /* [0, 320): literal/length + distance code lengths; [320, 339): the code length code's */
+  uint32_t mat[32];
+};
+
+/* the compressed stream of one member, in coordinates relative to its payload's address rounded down to 16 bytes */
+struct mk_bits {
+  const uint8_t *base; /* 16-byte aligned */
+  uint32_t *win;
+  uint32_t end;        /* first byte behind the payload */
+  uint32_t win_base, next, cnt;
+  uint64_t buf;
+  uint32_t lane;
+
+  __device__ __forceinline__ void stage() {
+    const uint32_t a = win_base + 16u * lane;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (a < end) v = *(const uint4 *)(base + a); /* (a 16-byte piece that starts inside the payload: inside the staging buffer, which ends in slack) */
+    mk_lds_fence();
+    ((uint4 *)win)[lane] = v;
+    mk_lds_fence();
+  }
+  __device__ __forceinline__ void seek(uint32_t a0) {
+    win_base = a0 & ~(MK_INFL_WIN - 1u);
+    stage();
+    const uint32_t w = mk_uni(win[(a0 & (MK_INFL_WIN - 1u)) >> 2]);
+    const uint32_t sh = 8u * (a0 & 3u);
+    buf = (uint64_t)(w >> sh);
+    cnt = 32u - sh;
+    next = (a0 & ~3u) + 4u;
+  }
+  /* at least 32 bits are in the buffer afterwards (zeros behind the payload's end: bitpos() tells) */
+  __device__ __forceinline__ void refill() {
+    if (cnt <= 32u) {
+      if (next - win_base == MK_INFL_WIN) { win_base = next; stage(); }
+      const uint32_t w = mk_uni(win[(next - win_base) >> 2]);
+      buf |= (uint64_t)w << cnt;
+      cnt += 32u;
+      next += 4u;
+    }
+  }
+  __device__ __forceinline__ uint32_t get(uint32_t n) {
+    const uint32_t v = (uint32_t)buf & ((1u << n) - 1u);
+    buf >>= n;
+    cnt -= n;
+    return v;
+  }
+  __device__ __forceinline__ uint64_t bitpos() const { return (uint64_t)next * 8u - cnt; }
+  __device__ __forceinline__ bool past_end() const { return bitpos() > (uint64_t)end * 8u; }
+};
+
+/* the canonical walk, a bit at a time (codes longer than the look-up table's index, and every code an incomplete set leaves out) */
+__device__ __forceinline__ int mk_decode_slow(mk_bits &b, const uint16_t *cnt, const uint16_t *sym) {
+  int code = 0, first = 0, index = 0;
+  for (uint32_t len = 1; len <= 15u; len++) {
+    code |= (int)b.get(1);
+    const int count = (int)mk_uni(cnt[len]);
+    if (code - count < first) return (int)mk_uni(sym[index + (code - first)]);
+    index += count;
+    first += count;
+    first <<= 1;
+    code <<= 1;
+  }
+  return -1;
+}
+__device__ __forceinline__ int mk_decode(mk_bits &b, const uint16_t *tab, uint32_t bits, const uint16_t *cnt, const uint16_t *sym) {
+  const uint32_t e = mk_uni(tab[(uint32_t)b.buf & ((1u << bits) - 1u)]);
+  const uint32_t l = e & 15u;
+  if (l) { b.buf >>= l; b.cnt -= l; return (int)(e >> 4); }
+  return mk_decode_slow(b, cnt, sym);
+}
+
+/* code tables of n symbols with the lengths lens[]: 0 ok, 1 over-subscribed, 2 incomplete (allowed only for a single code of
+ * length 1 or no code at all, as zlib does for literal/length and distance codes) */
+__device__ int mk_build(const uint8_t *lens, uint32_t n, uint16_t *cnt, uint16_t *sym, uint16_t *tab, uint32_t bits, bool single_ok, uint32_t lane) {
+  for (uint32_t i = lane; i < (1u << bits) / 2u; i += 64u) ((uint32_t *)tab)[i] = 0u;
+  uint32_t c = 0;
+  for (uint32_t s = 0; s < n; s++) c += (uint32_t)(lens[s] == lane); /* lane l: symbols of length l */
+  if (lane == 0u || lane > 15u) c = 0;
+  uint32_t offs = 0, first = 0, run = 0, code = 0, prevc = 0, maxlen = 0;
+  int left = 1;
+  bool over = false;
+  for (uint32_t l = 1; l < 16u; l++) {
+    const uint32_t cl = (uint32_t)__shfl((int)c, (int)l);
+    left = (left << 1) - (int)cl;
+    if (left < 0) over = true;
+    code = (code + prevc) << 1;
+    if (lane == l) { offs = run; first = code; }
+    run += cl;
+    prevc = cl;
+    if (cl) maxlen = l;
+  }
+  if (lane < 16u) cnt[lane] = (uint16_t)c;
+  if (over) return 1;
+  if (left > 0 && !(single_ok && maxlen <= 1u)) return 2;
+  if (c) { /* lanes 1..15 that have symbols: place them and fill the table */
+    uint32_t k = 0;
+    for (uint32_t s = 0; s < n && k < c; s++) {
+      if (lens[s] != lane) continue;
+      sym[offs + k] = (uint16_t)s;
+      if (lane <= bits) {
+        const uint32_t rev = __brev(first + k) >> (32u - lane);
+        for (uint32_t e = rev; e < (1u << bits); e += 1u << lane) tab[e] = (uint16_t)(s << 4 | lane);
+      }
+      k++;
+    }
+  }
+  mk_lds_fence();
+  return 0;
+}
+
+__global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_inflate_kernel(const uint8_t *__restrict__ comp, const mk_infl_blk *__restrict__ blks,
+                                                                         uint32_t nblocks, uint8_t *text, uint32_t *status) {
+  __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
+  __shared__ uint32_t crctab[256];
+  {
+    uint32_t c = threadIdx.x;
+    for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+    crctab[threadIdx.x] = c;
+  }
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t blk = blockIdx.x * MK_INFL_WAVES + wave;
+  if (blk >= nblocks) return;
+  mk_infl_lds &L = lds_all[wave];
+  const mk_infl_blk B = blks[blk];
+  const uint32_t isize = mk_uni(B.isize);
+  uint8_t *out = text + mk_uni(B.out_off);
+  const uint32_t shift = mk_uni(B.pay_off) & 15u;
+  mk_bits b;
+  b.base = comp + (mk_uni(B.pay_off) - shift);
+  b.win = L.win;
+  b.end = shift + mk_uni(B.pay_len);
+  b.lane = lane;
+  b.seek(shift);
+
+  uint32_t st = MK_INFL_OK, pos = 0, nlit = 0, synced = 0, lit = 0;
+  /* pending literals -> one store; false: they do not fit */
+  auto flush = [&]() -> bool {
+    if (nlit) {
+      if (pos + nlit > isize) { nlit = 0; return false; }
+      if (lane < nlit) out[pos + lane] = (uint8_t)lit;
+      pos += nlit;
+      nlit = 0;
+    }
+    return true;
+  };
+  uint32_t last = 0;
+  do {
+    b.refill();
+    if (b.past_end()) { st = MK_INFL_INPUT; break; }
+    last = b.get(1);
+    const uint32_t type = b.get(2);
+    if (type == 0u) { /* stored: LEN bytes behind LEN, NLEN at the next byte boundary */
+      b.get(b.cnt & 7u);
+      b.refill();
+      const uint32_t len = b.get(16), nlen = b.get(16);
+      if ((len ^ nlen) != 0xffffu) { st = MK_INFL_BAD_BLOCK; break; }
+      const uint32_t a0 = (uint32_t)(b.bitpos() >> 3);
+      if (b.past_end() || a0 + len > b.end) { st = MK_INFL_INPUT; break; }
+      if (!flush() || pos + len > isize) { st = MK_INFL_OUTPUT_LEN; break; }
+      for (uint32_t i = lane; i < len; i += 64u) out[pos + i] = b.base[a0 + i];
+      pos += len;
+      b.seek(a0 + len);
+      continue;
+    }
+    if (type == 3u) { st = MK_INFL_BAD_BLOCK; break; }
+    uint32_t nl = 288u, nd = 32u;
+    if (type == 1u) {
+      for (uint32_t i = lane; i < 320u; i += 64u) L.lens[i] = (uint8_t)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
+      mk_lds_fence();
+    } else {
+      nl = b.get(5) + 257u;
+      nd = b.get(5) + 1u;
+      const uint32_t nc = b.get(4) + 4u;
+      if (nl > 286u || nd > 30u) { st = MK_INFL_BAD_LENGTHS; break; }
+      if (lane < 19u) L.lens[320u + lane] = 0;
+      mk_lds_fence();
+      for (uint32_t i = 0; i < nc; i++) {
+        b.refill();
+        const uint32_t v = b.get(3);
+        if (lane == 0u) L.lens[320u + mk_clorder[i]] = (uint8_t)v;
+      }
+      mk_lds_fence();
+      /* the code length code borrows the distance code's arrays; 7 bits index its whole table */
+      if (mk_build(L.lens + 320, 19u, L.dist_cnt, L.dist_sym, L.dist_tab, 7u, false, lane)) { st = MK_INFL_BAD_CODE; break; }
+      uint32_t idx = 0, prev = 0;
+      while (idx < nl + nd) {
+        b.refill();
+        if (b.past_end()) { st = MK_INFL_INPUT; break; }
+        const int s = mk_decode(b, L.dist_tab, 7u, L.dist_cnt, L.dist_sym);
+        if (s < 0) { st = MK_INFL_BAD_CODE; break; }
+        if (s < 16) {
+          if (lane == 0u) L.lens[idx] = (uint8_t)s;
+          prev = (uint32_t)s;
+          idx++;
+          continue;
+        }
+        uint32_t rep, val = 0;
+        if (s == 16) {
+          if (idx == 0u) { st = MK_INFL_BAD_LENGTHS; break; }
+          val = prev;
+          rep = 3u + b.get(2);
+        } else if (s == 17) rep = 3u + b.get(3);
+        else rep = 11u + b.get(7);
+        if (idx + rep > nl + nd) { st = MK_INFL_BAD_LENGTHS; break; }
+        for (uint32_t i = lane; i < rep; i += 64u) L.lens[idx + i] = (uint8_t)val;
+        prev = val;
+        idx += rep;
+      }
+      if (st) break;
+      mk_lds_fence();
+      if (L.lens[256] == 0) { st = MK_INFL_BAD_LENGTHS; break; }
+    }
+    if (mk_build(L.lens, nl, L.lit_cnt, L.lit_sym, L.lit_tab, MK_INFL_LBITS, true, lane) ||
+        mk_build(L.lens + nl, nd, L.dist_cnt, L.dist_sym, L.dist_tab, MK_INFL_DBITS, true, lane)) { st = MK_INFL_BAD_CODE; break; }
+    /* the tokens of this block: each takes at least one bit of input */
+    for (;;) {
+      b.refill();
+      if (b.past_end()) { st = MK_INFL_INPUT; break; }
+      int s = mk_decode(b, L.lit_tab, MK_INFL_LBITS, L.lit_cnt, L.lit_sym);
+      if (s < 0) { st = MK_INFL_BAD_CODE; break; }
+      if (s < 256) {
+        if (lane == nlit) lit = (uint32_t)s;
+        if (++nlit == 64u && !flush()) { st = MK_INFL_OUTPUT_LEN; break; }
+        continue;
+      }
+      if (s == 256) break;
+      s -= 257;
+      if (s >= 29) { st = MK_INFL_BAD_CODE; break; }
+      const uint32_t len = (uint32_t)mk_lbase[s] + b.get(mk_lext[s]);
+      b.refill();
+      const int d = mk_decode(b, L.dist_tab, MK_INFL_DBITS, L.dist_cnt, L.dist_sym);
+      if (d < 0) { st = MK_INFL_BAD_CODE; break; }
+      if (d >= 30) { st = MK_INFL_BAD_DISTANCE; break; }
+      const uint32_t dist = (uint32_t)mk_dbase[d] + b.get(mk_dext[d]);
+      if (!flush()) { st = MK_INFL_OUTPUT_LEN; break; }
+      if (dist > pos) { st = MK_INFL_BAD_DISTANCE; break; }
+      if (pos + len > isize) { st = MK_INFL_OUTPUT_LEN; break; }
+      const uint32_t from = pos - dist;
+      if (from + (len < dist ? len : dist) > synced) { mk_store_fence(); synced = pos; } /* the source was written since the last wait */
+      if (dist >= len) { for (uint32_t i = lane; i < len; i += 64u) out[pos + i] = out[from + i]; }
+      else { for (uint32_t i = lane; i < len; i += 64u) out[pos + i] = out[from + i % dist]; }
+      pos += len;
+    }
+    if (st) break;
+  } while (!last);
+  if (!st && !flush()) st = MK_INFL_OUTPUT_LEN;
+  if (!st && b.past_end()) st = MK_INFL_INPUT;
+  if (!st && pos != isize) st = MK_INFL_OUTPUT_LEN;
+
+  if (!st) { /* CRC32 of out[0, isize) */
+    mk_store_fence();
+    uint32_t crc;
+    if (isize < 256u) {
+      uint32_t c = 0xffffffffu;
+      for (uint32_t i = 0; i < isize; i++) c = crctab[(c ^ out[i]) & 0xffu] ^ (c >> 8);
+      crc = ~c;
+    } else {
+      const uint32_t SL = (isize + 63u) / 64u, pad = 64u * SL - isize;
+      uint32_t r = 0;
+      for (uint32_t k = 0; k < SL; k++) {
+        const uint32_t p = lane * SL + k;
+        if (p >= pad) {
+          const uint32_t idx = p - pad;
+          uint32_t v = out[idx];
+          if (idx < 4u) v ^= 0xffu;
+          r = crctab[(r ^ v) & 0xffu] ^ (r >> 8);
+        }
+      }
+      { /* column j of "advance by SL zero bytes" */
+        uint32_t m = 1u << (lane & 31u);
+        for (uint32_t k = 0; k < SL; k++) m = crctab[m & 0xffu] ^ (m >> 8);
+        mk_lds_fence();
+        if (lane < 32u) L.mat[lane] = m;
+        mk_lds_fence();
+      }
+      for (uint32_t d = 1; d < 64u; d <<= 1) {
+        uint32_t t = 0, col = 0;
+        const uint32_t mine = L.mat[lane & 31u];
+        for (uint32_t bit = 0; bit < 32u; bit++) {
+          const uint32_t mb = L.mat[bit];
+          if ((r >> bit) & 1u) t ^= mb;
+          if ((mine >> bit) & 1u) col ^= mb;
+        }
+        const uint32_t u = (uint32_t)__shfl_up((int)t, d);
+        if ((lane & (2u * d - 1u)) == 2u * d - 1u) r ^= u;
+        mk_lds_fence();
+        if (lane < 32u) L.mat[lane] = col; /* the matrix squared: twice the distance at the next level */
+        mk_lds_fence();
+      }
+      crc = ~(uint32_t)__shfl((int)r, 63);
+    }
+    if (crc != mk_uni(B.crc)) st = MK_INFL_CRC;
+  }
+  if (lane == 0u) status[blk] = st;
+}
+
+/* ---- FASTQ framing of text in HBM ---------------------------------------------------------------------------------------------
+ * `buf` is a 16-byte aligned buffer, the text is buf[t0, e1); tiles and positions are in buffer coordinates, the buffer is
+ * allocated up to the end of the last tile (what lies outside [t0, e1) is loaded and masked, never used). */
+__device__ __forceinline__ uint32_t mk_nl4(uint32_t w) { /* bit k: byte k of w is '\n' */
+  const uint32_t x = w ^ 0x0a0a0a0au;
+  const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
+  return ((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u);
+}
+__device__ __forceinline__ uint64_t mk_fq_mask(const uint8_t *buf, uint32_t b, uint32_t t0, uint32_t e1) {
+  if (b >= e1 || b + 64u <= t0) return 0ull;
+  uint64_t m = 0;
+  const uint4 *p = (const uint4 *)(buf + b);
+  for (uint32_t q = 0; q < 4u; q++) {
+    const uint4 v = p[q];
+    const uint64_t n16 = (uint64_t)(mk_nl4(v.x) | mk_nl4(v.y) << 4 | mk_nl4(v.z) << 8 | mk_nl4(v.w) << 12);
+    m |= n16 << (16u * q);
+  }
+  if (t0 > b) m &= ~0ull << (t0 - b);
+  if (e1 - b < 64u) m &= (1ull << (e1 - b)) - 1ull;
+  return m;
+}
+__device__ __forceinline__ uint32_t mk_wave_sum(uint32_t v) {
+  for (int o = 32; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+  return v;
+}
+__device__ __forceinline__ uint32_t mk_wave_max(uint32_t v) {
+  for (int o = 32; o; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)v, o); v = u > v ? u : v; }
+  return v;
+}
+
+__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_count_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
+                                                                       uint32_t *tile_cnt, uint32_t *tile_last) {
+  const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * MK_FQ_WAVES + (threadIdx.x >> 6);
+  if (tile >= ntiles) return;
+  const uint32_t b = tile * MK_FQ_TILE + 64u * lane;
+  const uint64_t m = mk_fq_mask(buf, b, t0, e1);
+  const uint32_t c = mk_wave_sum((uint32_t)__popcll(m));
+  const uint32_t last = mk_wave_max(m ? b + (63u - (uint32_t)__clzll(m)) + 1u : 0u); /* position + 1; 0: none */
+  if (lane == 0u) { tile_cnt[tile] = c; tile_last[tile] = last; }
+}
+
+/* one workgroup of 1024 threads: tile_cnt becomes its exclusive prefix; the totals of the chunk */
+__global__ void __launch_bounds__(1024) mk_fq_scan_kernel(uint32_t *tile_cnt, const uint32_t *tile_last, uint32_t ntiles, uint32_t t0, uint32_t e1,
+                                                          int final, const uint32_t *status, uint32_t nblocks, mk_fq_res *res) {
+  __shared__ uint32_t sums[1024];
+  __shared__ uint32_t s_last, s_bad;
+  const uint32_t t = threadIdx.x;
+  if (t == 0u) { s_last = 0u; s_bad = 0xffffffffu; }
+  __syncthreads();
+  const uint32_t per = (ntiles + 1023u) / 1024u;
+  const uint32_t lo = t * per < ntiles ? t * per : ntiles, hi = lo + per < ntiles ? lo + per : ntiles;
+  uint32_t s = 0, lastp = 0;
+  for (uint32_t i = lo; i < hi; i++) { s += tile_cnt[i]; const uint32_t l = tile_last[i]; lastp = l > lastp ? l : lastp; }
+  sums[t] = s;
+  if (lastp) atomicMax(&s_last, lastp);
+  for (uint32_t i = t; i < nblocks; i += 1024u) if (status[i]) atomicMin(&s_bad, i);
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024u; d <<= 1) { /* inclusive scan */
+    const uint32_t v = t >= d ? sums[t - d] : 0u;
+    __syncthreads();
+    sums[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = sums[t] - s;
+  for (uint32_t i = lo; i < hi; i++) { const uint32_t c = tile_cnt[i]; tile_cnt[i] = run; run += c; }
+  if (t == 0u) {
+    const uint32_t n = e1 - t0, nl = sums[1023];
+    const uint32_t partial = s_last ? e1 - s_last : n; /* bytes behind the last newline */
+    const uint32_t lines = nl + (uint32_t)(final && partial > 0u);
+    mk_fq_res r;
+    r.nl = nl;
+    r.nrec = (final ? lines : nl) / 4u;
+    r.consumed = final ? n : 0u; /* (not final: the reduce kernel's thread that meets newline 4 * nrec - 1 says) */
+    r.maxline = final ? partial : 0u;
+    r.maxseq = 0u;
+    r.bad_block = s_bad;
+    r.bad_status = s_bad != 0xffffffffu ? status[s_bad] : 0u;
+    r.pad = 0u;
+    *res = r;
+  }
+}
+
+/* f(j, q, p) for every newline of the wave's tile, in the lane that holds it: p its position, j its number in the text (it ends
+ * line j), q the position of the newline in front of it (t0 - 1 for j == 0).  A line of more than MK_FQ_LINE_MAX bytes may be
+ * reported shorter, but never below MK_FQ_LINE_MAX + 1. */
+template <class F>
+__device__ __forceinline__ void mk_fq_walk(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t tile, uint32_t base, uint32_t lane, F f) {
+  const uint32_t b = tile * MK_FQ_TILE + 64u * lane;
+  uint64_t m = mk_fq_mask(buf, b, t0, e1);
+  const uint64_t have = __ballot(m != 0ull);
+  const uint32_t pc = (uint32_t)__popcll(m);
+  uint32_t ex = pc;
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)ex, o); if ((int)lane >= o) ex += u; }
+  ex -= pc;
+  const uint64_t before = have & ((1ull << lane) - 1ull);
+  const int src = before ? 63 - __clzll(before) : 0;
+  const uint32_t mlo = (uint32_t)__shfl((int)(uint32_t)m, src), mhi = (uint32_t)__shfl((int)(uint32_t)(m >> 32), src);
+  if (!m) return;
+  uint32_t j = base + ex;
+  int32_t q;
+  if (before) q = (int32_t)(tile * MK_FQ_TILE + 64u * (uint32_t)src + (63u - (uint32_t)__clzll((uint64_t)mhi << 32 | mlo)));
+  else if (j == 0u) q = (int32_t)t0 - 1;
+  else { /* the tile's first newline: its predecessor lies in front of the tile, at most a line away */
+    const int32_t s = (int32_t)(tile * MK_FQ_TILE) - 1;
+    int32_t lim = s - (int32_t)MK_FQ_LINE_MAX;
+    if (lim < (int32_t)t0) lim = (int32_t)t0;
+    q = s;
+    while (q >= lim && buf[q] != (uint8_t)'\n') q--;
+  }
+  while (m) {
+    const uint32_t p = b + (uint32_t)__builtin_ctzll(m);
+    f(j, q, p);
+    q = (int32_t)p;
+    j++;
+    m &= m - 1ull;
+  }
+}
+
+__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_reduce_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
+                                                                        const uint32_t *tile_base, int final, mk_fq_res *res) {
+  const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * MK_FQ_WAVES + (threadIdx.x >> 6);
+  if (tile >= ntiles) return;
+  const uint32_t nrec = res->nrec;
+  uint32_t maxline = 0, maxseq = 0;
+  mk_fq_walk(buf, t0, e1, tile, tile_base[tile], lane, [&](uint32_t j, int32_t q, uint32_t p) {
+    const uint32_t len = (uint32_t)((int32_t)p - q);
+    maxline = len > maxline ? len : maxline;
+    if ((j & 3u) == 1u && (j >> 2) < nrec) maxseq = len > maxseq ? len : maxseq;
+    if (!final && nrec && j == 4u * nrec - 1u) res->consumed = p + 1u - t0;
+  });
+  maxline = mk_wave_max(maxline);
+  maxseq = mk_wave_max(maxseq);
+  if (lane == 0u) {
+    if (maxline) atomicMax(&res->maxline, maxline);
+    if (maxseq) atomicMax(&res->maxseq, maxseq);
+  }
+}
+
+/* rows [r0, r1) of the chunk: row r is line 4r + 1 with its '\n', zero-padded to `stride` */
+__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_rows_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
+                                                                      const uint32_t *tile_base, uint32_t r0, uint32_t r1, uint32_t stride,
+                                                                      uint8_t *rows) {
+  __shared__ uint32_t ev_start[MK_FQ_WAVES][MK_FQ_TILE / 4], ev_len[MK_FQ_WAVES][MK_FQ_TILE / 4], ev_row[MK_FQ_WAVES][MK_FQ_TILE / 4];
+  __shared__ uint32_t ev_n[MK_FQ_WAVES];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, tile = blockIdx.x * MK_FQ_WAVES + wave;
+  if (tile >= ntiles) return;
+  if (lane == 0u) ev_n[wave] = 0u;
+  mk_lds_fence();
+  /* sequence lines end at least four bytes apart: a tile holds at most MK_FQ_TILE / 4 of them */
+  mk_fq_walk(buf, t0, e1, tile, tile_base[tile], lane, [&](uint32_t j, int32_t q, uint32_t p) {
+    const uint32_t r = j >> 2;
+    if ((j & 3u) != 1u || r < r0 || r >= r1) return;
+    const uint32_t at = atomicAdd(&ev_n[wave], 1u);
+    ev_start[wave][at] = (uint32_t)(q + 1);
+    ev_len[wave][at] = (uint32_t)((int32_t)p - q);
+    ev_row[wave][at] = r - r0;
+  });
+  mk_lds_fence();
+  const uint32_t n = ev_n[wave];
+  for (uint32_t e = 0; e < n; e++) {
+    const uint32_t start = ev_start[wave][e], row = ev_row[wave][e];
+    uint32_t len = ev_len[wave][e];
+    if (len > stride) len = stride; /* (cannot happen: the stride comes from the longest of these lines) */
+    uint32_t *dst = (uint32_t *)(rows + (uint64_t)row * stride);
+    for (uint32_t o = 4u * lane; o < stride; o += 256u) {
+      uint32_t w = 0;
+      for (uint32_t k = 0; k < 4u; k++) if (o + k < len) w |= (uint32_t)buf[start + o + k] << (8u * k);
+      dst[o >> 2] = w;
+    }
+  }
+}
+
+/* src[from, from + n) -> dst[to, to + n): the bytes behind a chunk's last complete record, n <= MK_FQ_CARRY */
+__global__ void __launch_bounds__(256) mk_fq_carry_kernel(const uint8_t *src, uint32_t from, uint8_t *dst, uint32_t to, uint32_t n) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[to + i] = src[from + i];
+}
+
+double mk_now_s() {
+  struct timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+
+} /* namespace */
+
+struct mk_inflate {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  /* the test entry points' buffers (mk_sketch_push_bgzf keeps its own) */
+  uint8_t *h_stage = nullptr, *d_comp = nullptr, *d_text = nullptr, *d_rows = nullptr;
+  uint64_t stage_cap = 0, comp_cap = 0, text_cap = 0, rows_cap = 0;
+  uint32_t *d_status = nullptr, *h_status = nullptr, *d_tile_cnt = nullptr, *d_tile_last = nullptr;
+  uint64_t status_cap = 0, h_status_cap = 0, tiles_cap = 0, tiles_last_cap = 0;
+  mk_fq_res *d_res = nullptr, *h_res = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  double inflate_ms = 0.0, frame_ms = 0.0;
+  char err[256] = {0};
+};
+
+static thread_local char mk_inflate_create_err[256];
+
+static int mk_infl_fail(mk_inflate *h, int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(h ? h->err : mk_inflate_create_err, 256, fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+#define MK_INFL_HIP(h, call)                                                                          \
+  do {                                                                                                \
+    hipError_t _r = (call);                                                                           \
+    if (_r != hipSuccess) return mk_infl_fail(h, MK_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
+  } while (0)
+
+template <class T>
+static int mk_infl_grow(mk_inflate *h, T **p, uint64_t *cap, uint64_t need) {
+  if (need == 0) need = 1;
+  if (need <= *cap && *p) return MK_OK;
+  (void)hipFree(*p);
+  *p = nullptr; *cap = 0;
+  const uint64_t c = need + need / 8 + 256;
+  MK_INFL_HIP(h, mk_dev_alloc(p, c * sizeof(T)));
+  *cap = c;
+  return MK_OK;
+}
+template <class T>
+static int mk_infl_grow_pinned(mk_inflate *h, T **p, uint64_t *cap, uint64_t need) {
+  if (need == 0) need = 1;
+  if (need <= *cap && *p) return MK_OK;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr; *cap = 0;
+  const uint64_t c = need + need / 8 + 256;
+  MK_INFL_HIP(h, mk_pin_alloc(p, c * sizeof(T), hipHostMallocDefault));
+  *cap = c;
+  return MK_OK;
+}
+
+extern "C" int mk_inflate_create(int device, mk_inflate **out) {
+  if (!out) return MK_ERR_ARG;
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return mk_infl_fail(nullptr, MK_ERR_NO_DEVICE, "no HIP device: mk_inflate has no CPU path");
+  if (device < 0 || device >= ndev) return mk_infl_fail(nullptr, MK_ERR_NO_DEVICE, "device %d out of range (0..%d)", device, ndev - 1);
+  mk_inflate *h = new (std::nothrow) mk_inflate();
+  if (!h) return MK_ERR_NOMEM;
+  h->device = device;
+  if (hipSetDevice(device) != hipSuccess) {
+    delete h;
+    return mk_infl_fail(nullptr, MK_ERR_NO_DEVICE, "hipSetDevice(%d) failed", device);
+  }
+  hipError_t r = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  if (r == hipSuccess) r = mk_dev_alloc(&h->d_res, sizeof(mk_fq_res));
+  if (r == hipSuccess) r = mk_pin_alloc(&h->h_res, sizeof(mk_fq_res), hipHostMallocDefault);
+  for (int i = 0; i < 4 && r == hipSuccess; i++) r = hipEventCreate(&h->ev[i]);
+  if (r != hipSuccess) {
+    mk_infl_fail(nullptr, MK_ERR_NOMEM, "inflate allocation: %s", hipGetErrorString(r));
+    mk_inflate_destroy(h);
+    return MK_ERR_NOMEM;
+  }
+  *out = h;
+  return MK_OK;
+}
+
+extern "C" int mk_inflate_destroy(mk_inflate *h) {
+  if (!h) return MK_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  void *dev[] = {h->d_comp, h->d_text, h->d_rows, h->d_status, h->d_tile_cnt, h->d_tile_last, h->d_res};
+  for (void *p : dev) (void)hipFree(p);
+  void *pin[] = {h->h_stage, h->h_status, h->h_res};
+  for (void *p : pin) if (p) (void)hipHostFree(p);
+  for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+  return MK_OK;
+}
+
+extern "C" const char *mk_inflate_last_error(const mk_inflate *h) { return h ? h->err : mk_inflate_create_err; }
+
+extern "C" int mk_inflate_last_kernel_ms(mk_inflate *h, double *inflate_ms, double *frame_ms) {
+  if (!h) return MK_ERR_ARG;
+  if (inflate_ms) *inflate_ms = h->inflate_ms;
+  if (frame_ms) *frame_ms = h->frame_ms;
+  return MK_OK;
+}
+
+/* ---- launches, on any stream ------------------------------------------------------------------------------------------------ */
+static hipError_t mk_launch_inflate(hipStream_t s, const uint8_t *d_comp, const mk_infl_blk *d_blks, uint32_t nblocks, uint8_t *d_text, uint32_t *d_status) {
+  if (!nblocks) return hipSuccess;
+  hipLaunchKernelGGL(mk_inflate_kernel, dim3((nblocks + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, s, d_comp, d_blks, nblocks, d_text, d_status);
+  return hipGetLastError();
+}
+static inline uint32_t mk_fq_ntiles(uint32_t e1) { return e1 ? (e1 + MK_FQ_TILE - 1) / MK_FQ_TILE : 1u; }
+/* bytes a text buffer needs for text that ends at buffer position e1: whole tiles */
+static inline uint64_t mk_fq_buf_bytes(uint64_t e1) { return ((e1 + MK_FQ_TILE - 1) / MK_FQ_TILE + 1) * (uint64_t)MK_FQ_TILE; }
+/* count + scan + reduce: *d_res is complete when the stream gets there */
+static hipError_t mk_launch_frame_count(hipStream_t s, const uint8_t *d_buf, uint32_t t0, uint32_t e1, int final, uint32_t *d_tile_cnt, uint32_t *d_tile_last,
+                                        const uint32_t *d_status, uint32_t nblocks, mk_fq_res *d_res) {
+  const uint32_t nt = mk_fq_ntiles(e1), grid = (nt + MK_FQ_WAVES - 1) / MK_FQ_WAVES;
+  hipLaunchKernelGGL(mk_fq_count_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, d_tile_cnt, d_tile_last);
+  hipLaunchKernelGGL(mk_fq_scan_kernel, dim3(1), dim3(1024), 0, s, d_tile_cnt, (const uint32_t *)d_tile_last, nt, t0, e1, final, d_status, nblocks, d_res);
+  hipLaunchKernelGGL(mk_fq_reduce_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, (const uint32_t *)d_tile_cnt, final, d_res);
+  return hipGetLastError();
+}
+static hipError_t mk_launch_frame_rows(hipStream_t s, const uint8_t *d_buf, uint32_t t0, uint32_t e1, const uint32_t *d_tile_cnt, uint32_t r0, uint32_t r1,
+                                       uint32_t stride, uint8_t *d_rows) {
+  if (r1 <= r0) return hipSuccess;
+  const uint32_t nt = mk_fq_ntiles(e1), grid = (nt + MK_FQ_WAVES - 1) / MK_FQ_WAVES;
+  hipLaunchKernelGGL(mk_fq_rows_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, d_tile_cnt, r0, r1, stride, d_rows);
+  return hipGetLastError();
+}
+static inline uint32_t mk_fq_stride(uint32_t maxseq) { const uint32_t need = maxseq ? maxseq : 1u; return MK_ROW_PITCH(need); }
+
+/* ---- the two entry points with a copy-back (tests, tools) ---------------------------------------------------------------------- */
+extern "C" int mk_inflate_blocks(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_bgzf_block *blocks, uint64_t nblocks,
+                                 uint8_t *out_host, size_t out_cap, uint32_t *status) {
+  if (!h || (!comp && comp_bytes) || (!blocks && nblocks) || !status) return MK_ERR_ARG;
+  if (nblocks == 0) return MK_OK;
+  if (nblocks > (1u << 24) || comp_bytes >= (1ull << 31)) return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_blocks: at most 2^24 members and 2 GiB a call");
+  uint64_t text_end = 0;
+  for (uint64_t i = 0; i < nblocks; i++) {
+    const mk_bgzf_block &b = blocks[i];
+    if (b.in_off + b.pay_off + (uint64_t)b.pay_len > comp_bytes || b.isize > 65536u || b.out_off + b.isize >= (1ull << 31))
+      return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_blocks: member %llu lies outside the buffers", (unsigned long long)i);
+    if (b.out_off + b.isize > text_end) text_end = b.out_off + b.isize;
+  }
+  if (out_host && out_cap < text_end) return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_blocks: out_cap too small");
+  MK_INFL_HIP(h, hipSetDevice(h->device));
+  const uint64_t tab_at = (comp_bytes + 15u) & ~(uint64_t)15u, stage_bytes = tab_at + nblocks * sizeof(mk_infl_blk);
+  int rc = mk_infl_grow_pinned(h, &h->h_stage, &h->stage_cap, stage_bytes);
+  if (!rc) rc = mk_infl_grow(h, &h->d_comp, &h->comp_cap, stage_bytes + 64);
+  if (!rc) rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(text_end));
+  if (!rc) rc = mk_infl_grow(h, &h->d_status, &h->status_cap, nblocks);
+  if (!rc) rc = mk_infl_grow_pinned(h, &h->h_status, &h->h_status_cap, nblocks);
+  if (rc) return rc;
+  memcpy(h->h_stage, comp, comp_bytes);
+  mk_infl_blk *tab = (mk_infl_blk *)(h->h_stage + tab_at);
+  for (uint64_t i = 0; i < nblocks; i++) {
+    const mk_bgzf_block &b = blocks[i];
+    tab[i] = mk_infl_blk{(uint32_t)(b.in_off + b.pay_off), b.pay_len, (uint32_t)b.out_off, b.isize, b.crc32};
+  }
+  MK_INFL_HIP(h, hipMemcpyAsync(h->d_comp, h->h_stage, stage_bytes, hipMemcpyHostToDevice, h->stream));
+  MK_INFL_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  MK_INFL_HIP(h, mk_launch_inflate(h->stream, h->d_comp, (const mk_infl_blk *)(h->d_comp + tab_at), (uint32_t)nblocks, h->d_text, h->d_status));
+  MK_INFL_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  MK_INFL_HIP(h, hipMemcpyAsync(h->h_status, h->d_status, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
+  memcpy(status, h->h_status, nblocks * sizeof(uint32_t));
+  if (out_host && text_end) MK_INFL_HIP(h, hipMemcpy(out_host, h->d_text, text_end, hipMemcpyDeviceToHost));
+  float ms = 0.f;
+  MK_INFL_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+  h->inflate_ms = ms;
+  return MK_OK;
+}
+
+extern "C" int mk_fastq_frame_device(mk_inflate *h, const uint8_t *text, size_t n, int final, uint8_t *rows_host, size_t rows_cap,
+                                     uint32_t *stride, uint64_t *nrows, size_t *consumed, uint32_t *longest) {
+  if (!h || (!text && n) || !stride || !nrows || !consumed) return MK_ERR_ARG;
+  if (n >= (1ull << 30)) return mk_infl_fail(h, MK_ERR_ARG, "mk_fastq_frame_device: at most 2^30 bytes a call");
+  MK_INFL_HIP(h, hipSetDevice(h->device));
+  const uint32_t t0 = 0, e1 = (uint32_t)n, nt = mk_fq_ntiles(e1);
+  int rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(e1));
+  if (!rc) rc = mk_infl_grow(h, &h->d_tile_cnt, &h->tiles_cap, nt);
+  if (!rc) rc = mk_infl_grow(h, &h->d_tile_last, &h->tiles_last_cap, nt);
+  if (rc) return rc;
+  if (n) MK_INFL_HIP(h, hipMemcpyAsync(h->d_text, text, n, hipMemcpyHostToDevice, h->stream));
+  MK_INFL_HIP(h, hipEventRecord(h->ev[2], h->stream));
+  MK_INFL_HIP(h, mk_launch_frame_count(h->stream, h->d_text, t0, e1, final != 0, h->d_tile_cnt, h->d_tile_last, nullptr, 0, h->d_res));
+  MK_INFL_HIP(h, hipMemcpyAsync(h->h_res, h->d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, h->stream));
+  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
+  const mk_fq_res r = *h->h_res;
+  if (longest) *longest = r.maxline;
+  *nrows = 0; *consumed = 0; *stride = mk_fq_stride(r.maxseq);
+  if (r.maxline >= MK_FQ_LINE_MAX) return mk_infl_fail(h, MK_ERR_FORMAT, "a FASTQ line of 4095 characters or more");
+  const uint32_t sd = mk_fq_stride(r.maxseq);
+  if (rows_host && (uint64_t)r.nrec * sd > rows_cap) return mk_infl_fail(h, MK_ERR_ARG, "mk_fastq_frame_device: %u rows of %u bytes do not fit rows_cap", r.nrec, sd);
+  rc = mk_infl_grow(h, &h->d_rows, &h->rows_cap, (uint64_t)r.nrec * sd);
+  if (rc) return rc;
+  MK_INFL_HIP(h, mk_launch_frame_rows(h->stream, h->d_text, t0, e1, h->d_tile_cnt, 0, r.nrec, sd, h->d_rows));
+  MK_INFL_HIP(h, hipEventRecord(h->ev[3], h->stream));
+  if (rows_host && r.nrec) MK_INFL_HIP(h, hipMemcpyAsync(rows_host, h->d_rows, (uint64_t)r.nrec * sd, hipMemcpyDeviceToHost, h->stream));
+  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  MK_INFL_HIP(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+  h->frame_ms = ms;
+  *nrows = r.nrec;
+  *consumed = r.consumed;
+  return MK_OK;
+}
+
+/* ---- the route bound to an engine -------------------------------------------------------------------------------------------- */
+namespace {
+struct mk_bgzf_run { /* everything mk_sketch_push_bgzf allocates, released on every way out */
+  mk_bgzf_block *blocks = nullptr;
+  hipStream_t copy = nullptr;
+  uint8_t *h_stage[2] = {nullptr, nullptr}, *d_comp[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr}, *d_rows = nullptr;
+  uint32_t *d_status[2] = {nullptr, nullptr}, *d_tile_cnt = nullptr, *d_tile_last = nullptr;
+  mk_fq_res *d_res = nullptr, *h_res = nullptr;
+  hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_res = nullptr, ev_i[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, ev_f[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~mk_bgzf_run() {
+    mk_bgzf_free(blocks);
+    for (int s = 0; s < 2; s++) {
+      if (h_stage[s]) (void)hipHostFree(h_stage[s]);
+      (void)hipFree(d_comp[s]); (void)hipFree(d_text[s]); (void)hipFree(d_status[s]);
+      if (ev_up[s]) (void)hipEventDestroy(ev_up[s]);
+      for (int k = 0; k < 2; k++) if (ev_i[s][k]) (void)hipEventDestroy(ev_i[s][k]);
+    }
+    (void)hipFree(d_rows); (void)hipFree(d_tile_cnt); (void)hipFree(d_tile_last); (void)hipFree(d_res);
+    if (h_res) (void)hipHostFree(h_res);
+    if (ev_res) (void)hipEventDestroy(ev_res);
+    for (hipEvent_t e : ev_f) if (e) (void)hipEventDestroy(e);
+    if (copy) (void)hipStreamDestroy(copy);
+  }
+};
+struct mk_bgzf_chunk { uint64_t b0, b1, in0, in1, text; };
+}
+
+static thread_local char mk_bgzf_err[256];
+#define MK_BGZF_HIP(call)                                                                                             \
+  do {                                                                                                                \
+    hipError_t _r = (call);                                                                                           \
+    if (_r != hipSuccess) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s: %s", #call, hipGetErrorString(_r)); (void)hipStreamSynchronize(S); if (R.copy) (void)hipStreamSynchronize(R.copy); return MK_ERR_HIP; } \
+  } while (0)
+
+extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, uint64_t first_ordinal, mk_bgzf_stats *st) {
+  if (!e || fd < 0) return MK_ERR_ARG;
+  mk_bgzf_stats stats;
+  memset(&stats, 0, sizeof stats);
+  stats.bad_block = -1;
+  if (st) *st = stats;
+  const double t_begin = mk_now_s();
+  mk_bgzf_run R;
+  uint64_t nblocks = 0, total = 0;
+  int is_bgzf = 0;
+  int rc = mk_bgzf_scan(fd, nullptr, size, &R.blocks, &nblocks, &total, &is_bgzf);
+  if (rc) return rc;
+  if (!is_bgzf) return MK_ERR_ARG;
+  stats.t_scan_s = mk_now_s() - t_begin;
+  void *sp = nullptr;
+  int device = 0;
+  rc = mk_engine_get_stream(e, &sp, &device);
+  if (rc) return rc;
+  hipStream_t S = (hipStream_t)sp;
+  /* chunks: runs of members whose text stays within chunk_bytes (at least one member each) */
+  uint64_t chunk_bytes = o && o->chunk_bytes ? o->chunk_bytes : (uint64_t)128 << 20;
+  if (chunk_bytes < 65536u) chunk_bytes = 65536u;
+  if (chunk_bytes > ((uint64_t)1 << 30)) chunk_bytes = (uint64_t)1 << 30;
+  std::vector<mk_bgzf_chunk> chunks;
+  uint64_t max_in = 0, max_text = 0, max_blocks = 0;
+  for (uint64_t b = 0; b < nblocks;) {
+    mk_bgzf_chunk c{b, b, R.blocks[b].in_off, 0, 0};
+    while (c.b1 < nblocks && (c.b1 == c.b0 || c.text + R.blocks[c.b1].isize <= chunk_bytes)) c.text += R.blocks[c.b1++].isize;
+    c.in1 = R.blocks[c.b1 - 1].in_off + R.blocks[c.b1 - 1].in_len;
+    if (c.in1 - c.in0 >= ((uint64_t)1 << 31)) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "a chunk of more than 2 GiB of compressed bytes"); return MK_ERR_ARG; }
+    max_in = c.in1 - c.in0 > max_in ? c.in1 - c.in0 : max_in;
+    max_text = c.text > max_text ? c.text : max_text;
+    max_blocks = c.b1 - c.b0 > max_blocks ? c.b1 - c.b0 : max_blocks;
+    chunks.push_back(c);
+    b = c.b1;
+  }
+  const uint64_t stage_bytes = ((max_in + 15u) & ~(uint64_t)15u) + max_blocks * sizeof(mk_infl_blk);
+  const uint64_t text_bytes = mk_fq_buf_bytes(MK_FQ_CARRY + max_text);
+  const uint32_t max_tiles = mk_fq_ntiles((uint32_t)(MK_FQ_CARRY + max_text));
+  const uint64_t rows_cap = (max_text + MK_FQ_CARRY > ((uint64_t)8 << 20) ? max_text + MK_FQ_CARRY : (uint64_t)8 << 20) + 4096u;
+  MK_BGZF_HIP(hipSetDevice(device));
+  MK_BGZF_HIP(hipStreamCreateWithFlags(&R.copy, hipStreamNonBlocking));
+  for (int s = 0; s < 2; s++) {
+    if (s == 1 && chunks.size() < 2) break;
+    MK_BGZF_HIP(mk_pin_alloc(&R.h_stage[s], stage_bytes, hipHostMallocDefault));
+    MK_BGZF_HIP(mk_dev_alloc(&R.d_comp[s], stage_bytes + 64));
+    MK_BGZF_HIP(mk_dev_alloc(&R.d_text[s], text_bytes));
+    MK_BGZF_HIP(mk_dev_alloc(&R.d_status[s], max_blocks * sizeof(uint32_t)));
+    MK_BGZF_HIP(hipEventCreateWithFlags(&R.ev_up[s], hipEventDisableTiming));
+    for (int k = 0; k < 2; k++) MK_BGZF_HIP(hipEventCreate(&R.ev_i[s][k]));
+  }
+  MK_BGZF_HIP(mk_dev_alloc(&R.d_rows, rows_cap));
+  MK_BGZF_HIP(mk_dev_alloc(&R.d_tile_cnt, (uint64_t)max_tiles * sizeof(uint32_t)));
+  MK_BGZF_HIP(mk_dev_alloc(&R.d_tile_last, (uint64_t)max_tiles * sizeof(uint32_t)));
+  MK_BGZF_HIP(mk_dev_alloc(&R.d_res, sizeof(mk_fq_res)));
+  MK_BGZF_HIP(mk_pin_alloc(&R.h_res, sizeof(mk_fq_res), hipHostMallocDefault));
+  MK_BGZF_HIP(hipEventCreateWithFlags(&R.ev_res, hipEventDisableTiming));
+  for (int k = 0; k < 4; k++) MK_BGZF_HIP(hipEventCreate(&R.ev_f[k]));
+
+  /* chunk k: file -> pinned staging -> device (copy stream), inflate behind it on the engine's stream */
+  auto queue_inflate = [&](size_t k) -> int {
+    const mk_bgzf_chunk &c = chunks[k];
+    const int s = (int)(k & 1u);
+    const double t0 = mk_now_s();
+    const uint64_t in_bytes = c.in1 - c.in0, tab_at = (in_bytes + 15u) & ~(uint64_t)15u;
+    for (uint64_t got = 0; got < in_bytes;) {
+      const ssize_t r = pread(fd, R.h_stage[s] + got, in_bytes - got, (off_t)(c.in0 + got));
+      if (r <= 0) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "reading the file failed"); (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); return MK_ERR_IO; }
+      got += (uint64_t)r;
+    }
+    mk_infl_blk *tab = (mk_infl_blk *)(R.h_stage[s] + tab_at);
+    for (uint64_t i = c.b0; i < c.b1; i++) {
+      const mk_bgzf_block &b = R.blocks[i];
+      tab[i - c.b0] = mk_infl_blk{(uint32_t)(b.in_off - c.in0 + b.pay_off), b.pay_len, (uint32_t)(MK_FQ_CARRY + (b.out_off - R.blocks[c.b0].out_off)), b.isize, b.crc32};
+    }
+    stats.t_read_s += mk_now_s() - t0;
+    const uint32_t nb = (uint32_t)(c.b1 - c.b0);
+    MK_BGZF_HIP(hipMemcpyAsync(R.d_comp[s], R.h_stage[s], tab_at + nb * sizeof(mk_infl_blk), hipMemcpyHostToDevice, R.copy));
+    MK_BGZF_HIP(hipEventRecord(R.ev_up[s], R.copy));
+    MK_BGZF_HIP(hipStreamWaitEvent(S, R.ev_up[s], 0));
+    MK_BGZF_HIP(hipEventRecord(R.ev_i[s][0], S));
+    MK_BGZF_HIP(mk_launch_inflate(S, R.d_comp[s], (const mk_infl_blk *)(R.d_comp[s] + tab_at), nb, R.d_text[s], R.d_status[s]));
+    MK_BGZF_HIP(hipEventRecord(R.ev_i[s][1], S));
+    return MK_OK;
+  };
+
+  rc = queue_inflate(0);
+  if (rc) return rc;
+  uint32_t carry = 0;
+  uint64_t ordinal = first_ordinal;
+  bool rows_timed = false;
+  int result = MK_OK;
+  for (size_t k = 0; k < chunks.size(); k++) {
+    const mk_bgzf_chunk &c = chunks[k];
+    const int s = (int)(k & 1u), final = k + 1 == chunks.size();
+    const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + (uint32_t)c.text, n = e1 - t0;
+    MK_BGZF_HIP(hipEventRecord(R.ev_f[0], S));
+    MK_BGZF_HIP(mk_launch_frame_count(S, R.d_text[s], t0, e1, final, R.d_tile_cnt, R.d_tile_last, R.d_status[s], (uint32_t)(c.b1 - c.b0), R.d_res));
+    MK_BGZF_HIP(hipEventRecord(R.ev_f[1], S));
+    MK_BGZF_HIP(hipMemcpyAsync(R.h_res, R.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
+    MK_BGZF_HIP(hipEventRecord(R.ev_res, S));
+    if (!final) { /* the next chunk's bytes travel and inflate beside this one's framing and scan (its slots were chunk k - 1's, whose read-back has been waited for) */
+      rc = queue_inflate(k + 1);
+      if (rc) return rc;
+    }
+    MK_BGZF_HIP(hipEventSynchronize(R.ev_res)); /* the one wait per chunk: rows, longest line, consumed, status */
+    const mk_fq_res r = *R.h_res;
+    float ms = 0.f;
+    MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_i[s][0], R.ev_i[s][1]));
+    stats.inflate_ms += ms;
+    MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_f[0], R.ev_f[1]));
+    stats.frame_ms += ms;
+    if (rows_timed) { MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_f[2], R.ev_f[3])); stats.frame_ms += ms; rows_timed = false; }
+    if (r.bad_block != 0xffffffffu) {
+      stats.bad_block = (int64_t)(c.b0 + r.bad_block);
+      stats.bad_status = (int32_t)r.bad_status;
+      snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "BGZF block %llu: %s", (unsigned long long)stats.bad_block, mk_inflate_status_text(stats.bad_status));
+      result = MK_ERR_FORMAT;
+      break;
+    }
+    if (r.maxline >= MK_FQ_LINE_MAX || (!final && n - r.consumed > MK_FQ_CARRY)) {
+      snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "a FASTQ line of 4095 characters or more");
+      result = MK_ERR_FORMAT;
+      break;
+    }
+    const uint32_t stride = mk_fq_stride(r.maxseq);
+    const uint32_t per = (uint32_t)(rows_cap / stride);
+    if (r.nrec) { MK_BGZF_HIP(hipEventRecord(R.ev_f[2], S)); }
+    for (uint32_t r0 = 0; r0 < r.nrec; r0 += per) {
+      const uint32_t r1 = r.nrec - r0 < per ? r.nrec : r0 + per;
+      MK_BGZF_HIP(mk_launch_frame_rows(S, R.d_text[s], t0, e1, R.d_tile_cnt, r0, r1, stride, R.d_rows));
+      if (r0 == 0) { MK_BGZF_HIP(hipEventRecord(R.ev_f[3], S)); rows_timed = true; }
+      rc = mk_sketch_push_reads_device(e, R.d_rows, stride, r1 - r0, ordinal);
+      if (rc) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
+      ordinal += r1 - r0;
+    }
+    stats.rows += r.nrec;
+    carry = n - r.consumed;
+    if (!final && carry) {
+      hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)R.d_text[s], t0 + r.consumed, R.d_text[s ^ 1], MK_FQ_CARRY - carry, carry);
+      MK_BGZF_HIP(hipGetLastError());
+    }
+  }
+  MK_BGZF_HIP(hipStreamSynchronize(S));
+  MK_BGZF_HIP(hipStreamSynchronize(R.copy));
+  if (rows_timed) { float ms = 0.f; MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_f[2], R.ev_f[3])); stats.frame_ms += ms; }
+  stats.blocks = nblocks; stats.chunks = chunks.size(); stats.comp_bytes = size; stats.text_bytes = total;
+  stats.t_total_s = mk_now_s() - t_begin;
+  if (st) *st = stats;
+  return result;
+}
+
+extern "C" const char *mk_bgzf_last_error(void) { return mk_bgzf_err; }
