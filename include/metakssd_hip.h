@@ -706,8 +706,8 @@ enum {
   MK_INFL_OK = 0,
   MK_INFL_BAD_BLOCK = 1,    /* deflate block type 3, or a stored block whose LEN and NLEN disagree */
   MK_INFL_BAD_LENGTHS = 2,  /* code length header: counts out of range, a repeat without a predecessor or past the end, no end-of-block code */
-  MK_INFL_BAD_CODE = 3,     /* over-subscribed or incomplete code, or a bit pattern / symbol no code assigns */
-  MK_INFL_BAD_DISTANCE = 4, /* distance beyond the start of the member's output */
+  MK_INFL_BAD_CODE = 3,     /* over-subscribed or incomplete code, a bit pattern no code assigns, or length symbol 286 / 287 (the fixed code has them) */
+  MK_INFL_BAD_DISTANCE = 4, /* distance beyond the start of the member's output, or distance symbol 30 / 31 (the fixed code has them) */
   MK_INFL_INPUT = 5,        /* the deflate stream needs more bytes than the member holds */
   MK_INFL_OUTPUT_LEN = 6,   /* the stream gives more or fewer bytes than ISIZE */
   MK_INFL_CRC = 7           /* the text's CRC32 is not the trailer's */

@@ -117,3 +117,76 @@ def test_inflate_has_no_cpu_path():
     with pytest.raises(capi.MkError) as ei:
         capi.Inflate(0)
     assert ei.value.code == capi.MK_ERR_NO_DEVICE and "no CPU path" in str(ei.value)
+
+
+# ---- the hand-made deflate streams of tests/test_gpu_bgzf.py: zlib says what they are -------------------------------------------------
+RANDOM = bytes(np.random.RandomState(77).randint(0, 256, 200000, dtype=np.uint8))
+LEGAL = {"long_codes": bz.legal_long_codes, "degenerate": bz.legal_degenerate, "header_ops": bz.legal_header_ops,
+         "length_258": bz.legal_length_258, "literal_runs": bz.legal_literal_runs, "random": lambda: bz.legal_random(RANDOM)}
+
+
+@pytest.mark.parametrize("group", sorted(LEGAL))
+def test_hand_made_legal_streams_are_what_zlib_reads(group):
+    cases = LEGAL[group]()
+    assert len({c[0] for c in cases}) == len(cases) >= 3
+    for c in cases:
+        name, raw, text = c[:3]
+        assert zlib.decompress(raw, -15) == text, name
+        assert gzip.decompress(bz.member_raw(raw, text)) == text, name
+        if len(c) > 3:
+            assert c[3](bz.parse_block_header(raw)), name  # the header does what the case is named for
+        if group == "random":
+            assert bz.first_block_type(raw) == 2 and len(set(text)) == 256, name
+
+
+@pytest.mark.parametrize("maxl,maxd,flip", [(15, 15, False), (15, 15, True), (10, 8, False), (11, 9, True)])
+def test_chain_case_decodes_a_symbol_at_every_code_length(maxl, maxd, flip):
+    lit_lens, dist_lens, tokens = bz.chain_case(maxl, maxd, 1, flip)
+    assert bz.kraft(lit_lens) == bz.kraft(dist_lens) == 32768
+    lit, dist = bz.used_symbols(tokens)
+    assert sorted({lit_lens[s] for s in lit}) == list(range(1, maxl + 1))
+    assert sorted({dist_lens[s] for s in dist}) == list(range(1, maxd + 1))
+    assert 2000 <= len(bz.apply_tokens(tokens)) <= 4500
+    w = bz.BitWriter()
+    bz.dynamic_block(w, lit_lens, dist_lens, tokens, 1)
+    h = bz.parse_block_header(w.done())
+    assert h["lit_lens"] == lit_lens and h["dist_lens"] == dist_lens
+
+
+def test_hand_made_illegal_streams_are_refused_by_zlib():
+    cases = bz.illegal_cases()
+    assert len({c[0] for c in cases}) == len(cases)
+    for name, member, raw, level, classes in cases:
+        assert capi.bgzf_scan(member + bz.EOF_MARKER) is not None, name  # the container is sound: the stream is what is wrong
+        if level == "stream":
+            with pytest.raises(zlib.error):
+                zlib.decompress(raw, -15)
+        else:  # a stream zlib reads, in a member whose ISIZE is one too small
+            assert level == "member" and classes == ("OUTPUT_LEN",)
+            assert len(zlib.decompress(raw, -15)) == struct.unpack("<I", member[-4:])[0] + 1, name
+            with pytest.raises(gzip.BadGzipFile):
+                gzip.decompress(member)
+        assert all(hasattr(capi, "MK_INFL_" + c) for c in classes)
+
+
+def test_window_sweep_hits_every_phase():
+    f, text, phases = bz.sweep_file(RANDOM)
+    assert gzip.decompress(f) == text
+    bz.assert_sweep_phases(phases)
+
+
+def test_hand_encoder_round_trips_a_fastq(tmp_path):
+    f = bz.hand_bgzf(RAGGED)
+    assert gzip.decompress(f) == RAGGED
+    table = capi.bgzf_scan(f)
+    assert table is not None and len(table) == (len(RAGGED) + 4095) // 4096 + 1
+    member, raw, starts = bz.hand_member(RAGGED[:4096])
+    assert zlib.decompress(raw, -15) == RAGGED[:4096]
+    heads = [bz.parse_block_header(raw, at) for at in starts]
+    assert [h["type"] for h in heads] == [0, 1, 2, 2] and [h["final"] for h in heads] == [0, 0, 0, 1]
+    assert all(max(h["lit_lens"]) == 15 for h in heads[2:])  # long-code sets
+    if shutil.which("zcat"):
+        p = tmp_path / "hand.fq.gz"
+        p.write_bytes(f)
+        r = subprocess.run(["zcat", "-fc", "--", str(p)], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        assert r.returncode == 0 and r.stdout == RAGGED

@@ -124,6 +124,78 @@ def test_inflate_damaged_members_give_a_status_not_a_fault(infl):
     assert st == [capi.MK_INFL_BAD_BLOCK, capi.MK_INFL_BAD_BLOCK]
 
 
+# ---- hand-made deflate streams: what no zlib compressor emits (tests/test_bgzf_host.py holds every one of them against zlib) ------------
+def check_cases(infl, cases):
+    """one launch: a member per case, the end marker last; a failing member is named"""
+    f = b"".join(bz.member_raw(c[1], c[2]) for c in cases) + bz.EOF_MARKER
+    table = capi.bgzf_scan(f)
+    assert table is not None and [t["isize"] for t in table] == [len(c[2]) for c in cases] + [0]
+    got, st = infl.blocks(f, table)
+    bad = [(c[0], capi.lib.mk_inflate_status_text(s).decode()) for c, s in zip(cases, st) if s]
+    bad += [c[0] for c, t in zip(cases, table) if got[t["out_off"]:t["out_off"] + t["isize"]] != c[2]]
+    assert not bad, bad
+    check_inflate(infl, f, table, b"".join(c[2] for c in cases))
+
+
+def test_inflate_code_lengths_1_to_15_and_both_sides_of_the_tables(infl):
+    check_cases(infl, bz.legal_long_codes())
+
+
+def test_inflate_degenerate_distance_sets_and_an_empty_block(infl):
+    check_cases(infl, bz.legal_degenerate())
+
+
+def test_inflate_code_length_runs_across_the_alphabets_and_hclen(infl):
+    check_cases(infl, bz.legal_header_ops())
+
+
+def test_inflate_length_258_as_symbol_285_and_as_284(infl):
+    check_cases(infl, bz.legal_length_258())
+
+
+def test_inflate_literal_runs_around_the_register_then_a_match(infl):
+    check_cases(infl, bz.legal_literal_runs())
+
+
+def test_inflate_random_bytes_through_huffman_tables(infl):
+    cases = bz.legal_random(RANDOM)
+    assert [bz.first_block_type(c[1]) for c in cases] == [2, 2, 2]
+    check_cases(infl, cases)
+
+
+def test_inflate_maximal_tokens_at_every_phase_of_the_window(infl):
+    f, text, phases = bz.sweep_file(RANDOM)
+    bz.assert_sweep_phases(phases)  # computed from the written bits, whatever the kernel does
+    table = capi.bgzf_scan(f)
+    assert table is not None and len(table) == len(phases) + 2
+    assert [(t["pay_off"], t["in_off"]) for t in table[1:-1]] == [(p, i) for _, _, p, i in phases]
+    got, st = infl.blocks(f, table)
+    bad = [(ph, s) for ph, s, t in zip(phases, st[1:], table[1:]) if s or got[t["out_off"]:t["out_off"] + t["isize"]] != text[t["out_off"]:t["out_off"] + t["isize"]]]
+    assert not bad, bad[:8]
+    check_inflate(infl, f, table, text)
+
+
+def test_inflate_malformed_streams_give_their_status_and_spare_the_neighbours(infl):
+    cases = bz.illegal_cases()
+    goods = [bz.golden_text("fq_ragged")[300 * i:300 * i + 250 + i] for i in range(len(cases) + 1)]
+    f = bz.member(goods[0])
+    for c, g in zip(cases, goods[1:]):
+        f += c[1] + bz.member(g, 1 + len(g) % 9)
+    f += bz.EOF_MARKER
+    table = capi.bgzf_scan(f)
+    assert table is not None and len(table) == 2 * len(cases) + 2
+    got, st = infl.blocks(f, table)
+    for i, g in enumerate(goods):
+        t = table[2 * i]
+        assert st[2 * i] == 0 and got[t["out_off"]:t["out_off"] + t["isize"]] == g, "the good member %d" % i
+    wrong = []
+    for i, (name, member, raw, level, classes) in enumerate(cases):
+        s = st[2 * i + 1]
+        if s == 0 or s not in [getattr(capi, "MK_INFL_" + c) for c in classes]:
+            wrong.append((name, capi.lib.mk_inflate_status_text(s).decode(), classes))
+    assert not wrong, wrong
+
+
 # ---- the framer against the host ---------------------------------------------------------------------------------------------------
 def host_rows(text):
     """mk_fastq_frame over the whole text, final: the sequence lines with their '\\n', and the bytes consumed"""
@@ -334,3 +406,25 @@ def test_cli_damaged_bgzf_fails_loudly(damage, shuf_files, tmp_path):
     if damage == "isize":
         assert "output length" in err
     assert not os.path.exists(os.path.join(out, "cofiles.stat"))
+
+
+def test_cli_hand_written_members_equal_zcat_route_and_reference(shuf_files, tmp_path):
+    case = "ragged500_L1K7"
+    entry = MANIFEST["cases"][case]
+    text = golden_text_of(case)
+    assert text == bz.golden_text("fq_ragged") and entry["flags"] == ["-A"]
+    inp = str(tmp_path / "hand.fq.gz")
+    open(inp, "wb").write(bz.hand_bgzf(text, 4096))
+    shuf = shuf_files(entry["shuf"])
+    base, out = str(tmp_path / "zcat"), str(tmp_path / "dev")
+    r, routes = run_cli(shuf, entry["flags"], base, inp, ["--no-device-inflate"])
+    assert r.returncode == 0, r.stderr.decode()
+    assert [x["route"] for x in routes] == ["zcat"]
+    r, routes = run_cli(shuf, entry["flags"], out, inp)
+    assert r.returncode == 0, r.stderr.decode()
+    assert [x["route"] for x in routes] == ["device-inflate"]
+    assert routes[0]["text_bytes"] == len(text) and routes[0]["blocks"] == (len(text) + 4095) // 4096 + 1
+    same_dir(base, out)
+    exp = os.path.join(gc.GOLDEN, "expected", case)
+    for f in entry["files"]:
+        assert filecmp.cmp(os.path.join(exp, f), os.path.join(out, f), shallow=False), f
