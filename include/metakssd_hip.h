@@ -710,7 +710,9 @@ enum {
   MK_INFL_BAD_DISTANCE = 4, /* distance beyond the start of the member's output, or distance symbol 30 / 31 (the fixed code has them) */
   MK_INFL_INPUT = 5,        /* the deflate stream needs more bytes than the member holds */
   MK_INFL_OUTPUT_LEN = 6,   /* the stream gives more or fewer bytes than ISIZE */
-  MK_INFL_CRC = 7           /* the text's CRC32 is not the trailer's */
+  MK_INFL_CRC = 7,          /* the text's CRC32 is not the trailer's */
+  MK_INFL_TRAILING = 8      /* (plain gzip only) the stream's final block ends before the payload does: more members follow, the
+                             * file is legal multi-member gzip and not one the device route takes */
 };
 const char *mk_inflate_status_text(int status);
 typedef struct mk_inflate mk_inflate;
@@ -757,6 +759,65 @@ const char *mk_bgzf_last_error(void); /* text of the calling thread's last faile
 /* the stream the engine's kernels are queued on now and its device, for work that must be ordered with them (staged rows are
  * flushed first).  MK_ERR_STATE with MK_OPT_SPLIT_CUS (two queues: no single stream orders with the scan). */
 int mk_engine_get_stream(mk_engine *e, void **hip_stream, int *device);
+
+/* ---- plain gzip FASTA inflated on the device, one wavefront per file (a directory of `.fna.gz` genomes; replaces one `zcat -fc`
+ * child per file) ---------------------------------------------------------------------------------------------------------
+ *   mk_gzip_scan              host: header and trailer of a single-member gzip file
+ *   mk_inflate_members        device: one wavefront inflates one member of any size; the CRC32 of every text by many waves per
+ *                             text (slices of MK_CRC_SLICE bytes, combined per file), compared with the trailer on the device
+ *   mk_sketch_batch_begin_gz  a batch of files whose text is made on the device; results through mk_sketch_batch_end */
+typedef struct mk_gzip_info {
+  uint64_t pay_off, pay_len; /* the deflate stream: [pay_off, pay_off + pay_len) of the file, ending 8 bytes before its end */
+  uint32_t crc32, isize;     /* the trailer */
+  int32_t is_single;         /* != 0: the shape below; 0: everything else is zero, the file is not for the device */
+  int32_t reserved;
+} mk_gzip_info;
+/* The file is `size` bytes at `mem`, or (mem == NULL) behind the descriptor fd.  is_single = 1 when it starts 1f 8b 08, its FLG
+ * has the reserved bits zero, its optional fields (FEXTRA, FNAME, FCOMMENT, FHCRC -- skipped, the header CRC is not verified)
+ * end inside the file, at least one payload byte lies between them and the last 8 bytes, and 1 <= ISIZE <= MK_BATCH_FILE_MAX.
+ * Everything else -- a header that runs past the file, reserved bits, CM != 8, an empty file, ISIZE 0, another format -- is
+ * is_single = 0 with MK_OK: not an error, the caller keeps the zcat route.  A concatenation of members passes this scan (its payload
+ * range then spans all of them but the last trailer); the decode reports it as MK_INFL_TRAILING.  Host code only. */
+int mk_gzip_scan(int fd, const uint8_t *mem, size_t size, mk_gzip_info *out);
+
+#define MK_CRC_SLICE 16384u /* text bytes one wavefront of the CRC kernel takes */
+typedef struct mk_gz_member {
+  uint64_t pay_off;  /* the deflate stream in `comp` */
+  uint64_t out_off;  /* where its text goes in the output: the caller keeps the places apart */
+  uint32_t pay_len, isize, crc32;
+  uint32_t reserved;
+} mk_gz_member;
+typedef struct mk_gz_member_result {
+  uint32_t status;   /* MK_INFL_* */
+  uint32_t consumed; /* bytes of the payload the decode used (whole bytes, the last one rounded up) */
+  uint32_t pos;      /* text bytes written */
+  uint32_t crc32;    /* CRC32 of the isize bytes at the member's place, whatever the status */
+} mk_gz_member_result;
+/* As mk_inflate_blocks for members of any size up to MK_BATCH_FILE_MAX (the text of all of them below 2^30 bytes): one wavefront
+ * decodes one member from start to end WITHOUT the in-wave CRC; mk_crc32_files_kernel then takes every text in slices of
+ * MK_CRC_SLICE bytes, a wave per slice, a second kernel combines a file's slices (one thread per file, no atomics) and folds the
+ * comparison with the trailer into the status.  Statuses in order of precedence: what the decode met (MK_INFL_BAD_* / _INPUT /
+ * _OUTPUT_LEN when the stream gives more than ISIZE bytes), MK_INFL_TRAILING (the final block ended before the payload: a
+ * multi-member file whose first member fits), MK_INFL_OUTPUT_LEN (fewer bytes than ISIZE), MK_INFL_CRC.  Damage is a status, never
+ * a fault: loads stay inside a payload rounded to 16 bytes, stores inside the ISIZE bytes of the member's place. */
+int mk_inflate_members(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_gz_member *members, uint32_t nmembers,
+                       uint8_t *out_host, size_t out_cap, mk_gz_member_result *res);
+
+typedef struct mk_gz_file {
+  const uint8_t *comp; /* the whole file as it lies on disk */
+  uint64_t n;          /* its bytes */
+  mk_gzip_info info;   /* what mk_gzip_scan said about them (is_single != 0) */
+} mk_gz_file;
+/* mk_sketch_batch_begin for files that are single-member gzip: the compressed bytes cross PCIe through pinned staging (one copy
+ * when every file starts where the one in front ends, rounded up to 16 bytes), every file's text place in the batch's text
+ * buffer is a prefix sum of the ISIZEs rounded up to 1024 bytes, inflate and CRC run on the engine's stream and the FASTA walk,
+ * scan and finish of mk_sketch_batch_begin follow unchanged.  Limits as there, counted in TEXT bytes (ISIZE).  Results:
+ * mk_sketch_batch_end; a file whose inflate status is not MK_INFL_OK gets status MK_ERR_FORMAT and an empty result (its place is
+ * never read as sketch input; the other files are unaffected), the status itself through mk_sketch_batch_gz_status.
+ * The files' bytes may be reused as soon as this call returns.  Engines with MK_OPT_SPLIT_CUS: MK_ERR_STATE. */
+int mk_sketch_batch_begin_gz(mk_engine *e, int mode, const mk_gz_file *files, uint32_t nfiles);
+/* MK_INFL_* of every file of the batch the LAST mk_sketch_batch_end handed out (zeros when that was not a gz batch) */
+int mk_sketch_batch_gz_status(mk_engine *e, uint32_t *status, uint32_t nfiles);
 
 /* distance.out (host).  Options as command_dist_wrapper.c:83-92. */
 typedef struct mk_dist_opts {

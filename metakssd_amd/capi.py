@@ -105,6 +105,24 @@ class BgzfBlockC(C.Structure):
                 ("crc32", C.c_uint32), ("isize", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class GzipInfoC(C.Structure):
+    _fields_ = [("pay_off", C.c_uint64), ("pay_len", C.c_uint64), ("crc32", C.c_uint32), ("isize", C.c_uint32), ("is_single", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class GzMemberC(C.Structure):
+    _fields_ = [("pay_off", C.c_uint64), ("out_off", C.c_uint64), ("pay_len", C.c_uint32), ("isize", C.c_uint32), ("crc32", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class GzMemberResultC(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("consumed", C.c_uint32), ("pos", C.c_uint32), ("crc32", C.c_uint32)]
+
+
+class GzFileC(C.Structure):
+    _fields_ = [("comp", C.c_void_p), ("n", C.c_uint64), ("info", GzipInfoC)]
+
+
 class BgzfOptsC(C.Structure):
     _fields_ = [("chunk_bytes", C.c_uint64), ("reserved", C.c_uint64)]
 
@@ -149,6 +167,10 @@ def _load():
         "mk_sketch_batch_begin_rows": [vp, C.c_int, u32, vp, u32],
         "mk_fasta_pack_rows": [vp, C.c_size_t, C.c_int32, u32, vp, u64, C.POINTER(u64)],
         "mk_sketch_batch_end": [vp, vp],
+        "mk_sketch_batch_begin_gz": [vp, C.c_int, C.POINTER(GzFileC), u32],
+        "mk_sketch_batch_gz_status": [vp, vp, u32],
+        "mk_gzip_scan": [C.c_int, vp, C.c_size_t, C.POINTER(GzipInfoC)],
+        "mk_inflate_members": [vp, vp, C.c_size_t, C.POINTER(GzMemberC), u32, vp, C.c_size_t, C.POINTER(GzMemberResultC)],
         "mk_sketch_finish": [vp, C.POINTER(ResultC)],
         "mk_sketch_finish_begin": [vp],
         "mk_sketch_finish_end": [vp, C.POINTER(ResultC)],
@@ -649,6 +671,39 @@ class Engine:
         self._batches = getattr(self, "_batches", [])
         self._batches.append((keep, n))
 
+    def batch_begin_gz(self, gz_files, mode=MK_MODE_SET, one_buffer=False):
+        """mk_sketch_batch_begin_gz over a list of byte strings, each a gzip file mk_gzip_scan accepts.  one_buffer: the files lie in ONE
+        16-byte aligned buffer at 1 KiB-aligned offsets (copied from where they are) instead of separate arrays (packed into staging)."""
+        n = len(gz_files)
+        files = (GzFileC * n)()
+        if one_buffer:
+            offs, at = [], 0
+            for t in gz_files:
+                offs.append(at)
+                at += (len(t) + 1023) // 1024 * 1024
+            raw = np.zeros(at + 1024 + 16, dtype=np.uint8)
+            base = (-raw.ctypes.data) % 16
+            for t, o in zip(gz_files, offs):
+                raw[base + o:base + o + len(t)] = np.frombuffer(bytes(t), dtype=np.uint8)
+            ptrs = [raw.ctypes.data + base + o for o in offs]
+            keep = [raw]
+        else:
+            keep = [np.frombuffer(bytes(t), dtype=np.uint8).copy() for t in gz_files]
+            ptrs = [a.ctypes.data for a in keep]
+        for i, t in enumerate(gz_files):
+            files[i].comp = ptrs[i]
+            files[i].n = len(t)
+            _check(lib.mk_gzip_scan(-1, ptrs[i], len(t), C.byref(files[i].info)))
+        _check(lib.mk_sketch_batch_begin_gz(self.h, mode, files, n), self.h)
+        self._batches = getattr(self, "_batches", [])
+        self._batches.append((keep, n))
+
+    def batch_gz_status(self, n):
+        """MK_INFL_* per file of the batch the last batch_end() handed out"""
+        st = np.zeros(max(1, n), dtype=np.uint32)
+        _check(lib.mk_sketch_batch_gz_status(self.h, st.ctypes.data, n), self.h)
+        return [int(x) for x in st[:n]]
+
     def batch_end(self):
         """-> per file (status, alone, [ids per component]) of the oldest batch in flight"""
         if not getattr(self, "_batches", None):  # nothing in flight: let the library say so
@@ -1120,6 +1175,8 @@ MK_BYREAD_MAX_PUSH = 8 << 20
 
 
 MK_INFL_OK, MK_INFL_BAD_BLOCK, MK_INFL_BAD_LENGTHS, MK_INFL_BAD_CODE, MK_INFL_BAD_DISTANCE, MK_INFL_INPUT, MK_INFL_OUTPUT_LEN, MK_INFL_CRC = range(8)
+MK_INFL_TRAILING = 8
+MK_CRC_SLICE = 16384
 BGZF_FIELDS = ("in_off", "out_off", "in_len", "pay_off", "pay_len", "crc32", "isize")
 
 
@@ -1142,6 +1199,25 @@ def bgzf_scan(data=None, path=None):
     assert total.value == sum(x["isize"] for x in out)
     lib.mk_bgzf_free(tab)
     return out
+
+
+def gzip_scan(data=None, path=None):
+    """mk_gzip_scan over bytes or over a file -> dict(pay_off, pay_len, crc32, isize), or None when the file is not a single-member
+    gzip file for the device route.  Host code: no GPU needed."""
+    info = GzipInfoC()
+    if path is not None:
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            _check(lib.mk_gzip_scan(fd, None, os.fstat(fd).st_size, C.byref(info)))
+        finally:
+            os.close(fd)
+    else:
+        b = np.frombuffer(bytes(data), dtype=np.uint8)
+        _check(lib.mk_gzip_scan(-1, b.ctypes.data if len(b) else C.c_void_p(1), len(b), C.byref(info)))
+    if not info.is_single:
+        assert (info.pay_off, info.pay_len, info.crc32, info.isize) == (0, 0, 0, 0)
+        return None
+    return {"pay_off": int(info.pay_off), "pay_len": int(info.pay_len), "crc32": int(info.crc32), "isize": int(info.isize)}
 
 
 class Inflate:
@@ -1170,6 +1246,21 @@ class Inflate:
         st = np.full(max(1, n), 0xFFFFFFFF, dtype=np.uint32)
         self._check(lib.mk_inflate_blocks(self.h, b.ctypes.data, len(b), arr, n, out.ctypes.data, end, st.ctypes.data))
         return out[:end].tobytes(), [int(x) for x in st[:n]]
+
+    def members(self, comp, table):
+        """mk_inflate_members.  comp: bytes, table: dicts (pay_off, pay_len, out_off, isize, crc32) ->
+        (text bytes, [(status, consumed, pos, crc32) per member])"""
+        b = np.frombuffer(bytes(comp), dtype=np.uint8)
+        n = len(table)
+        arr = (GzMemberC * max(1, n))()
+        for i, t in enumerate(table):
+            for f in ("pay_off", "pay_len", "out_off", "isize", "crc32"):
+                setattr(arr[i], f, t[f])
+        end = max([t["out_off"] + t["isize"] for t in table] + [0])
+        out = np.zeros(max(1, end), dtype=np.uint8)
+        res = (GzMemberResultC * max(1, n))()
+        self._check(lib.mk_inflate_members(self.h, b.ctypes.data if len(b) else None, len(b), arr, n, out.ctypes.data, end, res))
+        return out[:end].tobytes(), [(int(r.status), int(r.consumed), int(r.pos), int(r.crc32)) for r in res[:n]]
 
     def frame(self, text, final=True):
         """mk_fastq_frame_device -> (rows u8 [nrows * stride], stride, nrows, consumed, longest line, rc)"""

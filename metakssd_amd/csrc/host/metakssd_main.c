@@ -151,6 +151,9 @@ static int g_early_chunks = 96; /* --early-chunks: chunks of a FASTQ file framed
 static int g_frame_early = 0; /* --frame-early: every chunk of a FASTQ file may be framed at once, also while the runtime and the engine come up (measurement) */
 static int g_ahead = MK_DEFAULT_AHEAD; /* --ahead: row buffers the FASTQ stream's framers may run ahead of the pushes by */
 static int g_no_device_inflate = 0; /* --no-device-inflate: BGZF inputs through `zcat -fc` like every other .gz (measurement) */
+static int g_gz_batches = 0;        /* --device-inflate: single-member .gz genomes of a directory travel in gz batches and are inflated on the device.
+                                     * Off by default: one wavefront decodes 7 MB/s, a batch of 64 genomes of 4 MB takes 0.54 s, and sixteen zcat
+                                     * children are 6-14 times faster on 1 024 genomes */
 static uint64_t g_inflate_chunk_bytes = 0; /* --inflate-chunk-kib: text bytes per chunk of the device route (test hook; 0 = the library's default) */
 static int g_timing = 0; /* --timing */
 static int g_component_sz = 8; /* --component-sz: the reference's compile-time COMPONENT_SZ (global_basic.h:35-37) */
@@ -612,14 +615,18 @@ static int sketch_fastq_mapped(ctx_t *c, const char *path) {
   return 1;
 }
 
-/* --timing: which way a compressed FASTQ went, one JSON line per input */
+/* --timing: which way a compressed input went, one JSON line per input.  g_gz_fallback: the device route was tried first and gave
+ * this inflate status (a gzip genome that came back from its batch, see the batch driver) */
+static const char *g_gz_fallback = NULL;
 static void report_route(const char *path, const char *route, const mk_bgzf_stats *bs) {
   if (!g_timing) return;
+  char fb[160] = "";
+  if (g_gz_fallback) snprintf(fb, sizeof fb, ", \"fallback\": \"%s\"", g_gz_fallback);
   printf("{\"input\": \"%s\", \"route\": \"%s\", \"blocks\": %llu, \"chunks\": %llu, \"comp_bytes\": %llu, \"text_bytes\": %llu, \"rows\": %llu, "
-         "\"inflate_ms\": %.3f, \"frame_ms\": %.3f, \"bgzf_scan_s\": %.4f, \"read_s\": %.4f, \"route_total_s\": %.4f}\n",
+         "\"inflate_ms\": %.3f, \"frame_ms\": %.3f, \"bgzf_scan_s\": %.4f, \"read_s\": %.4f, \"route_total_s\": %.4f%s}\n",
          path, route, bs ? (unsigned long long)bs->blocks : 0ull, bs ? (unsigned long long)bs->chunks : 0ull, bs ? (unsigned long long)bs->comp_bytes : 0ull,
          bs ? (unsigned long long)bs->text_bytes : 0ull, bs ? (unsigned long long)bs->rows : 0ull, bs ? bs->inflate_ms : 0.0, bs ? bs->frame_ms : 0.0,
-         bs ? bs->t_scan_s : 0.0, bs ? bs->t_read_s : 0.0, bs ? bs->t_total_s : 0.0);
+         bs ? bs->t_scan_s : 0.0, bs ? bs->t_read_s : 0.0, bs ? bs->t_total_s : 0.0, fb);
 }
 
 /* a .gz that is a BGZF chain from its first byte to its last (mk_bgzf_scan) is inflated, checked and framed on the device; 0: not
@@ -2118,6 +2125,7 @@ static void sketch_file_push(ctx_t *c, const job_opts *o, int i, int *held_out) 
   c->occ = fq && !abundance; c->qmin = o->kmerqlty; c->TL = o->P->TL; c->nthreads = o->nthreads;
   int handled = 0, held = -1;
   pf_t *pf = o->pf;
+  if (!fq && is_compressed(path)) report_route(path, "zcat", NULL); /* (a FASTQ input says so where its reader is chosen) */
   if (o->nworkers) {
     pthread_mutex_lock(&pf->mu);
     while (!pf->slots[i].ready) pthread_cond_wait(&pf->cv_ready, &pf->mu);
@@ -2288,11 +2296,13 @@ static int g_batch_files = 256;                  /* --batch-files */
 static int g_batch_narrow = 0;                   /* --batch-narrow: rows of 152 bases (the FASTQ rows) instead of wide rows of 240 */
 static int g_batch_text = 0;                     /* --batch-text: the files' TEXT goes to the device (which then does the FASTA walk too) */
 
-typedef struct { int first, n, batch; } bjob;    /* files [first, first + n); batch: its number among the batches, -1 = one file alone */
+typedef struct { int first, n, batch, gz, nsub; } bjob; /* files [first, first + n); batch: its number among the batches, -1 = one file alone;
+                                                         * gz: single-member gzip files, inflated on the device; nsub: files the engine got */
 typedef struct {
   strlist *files;
   uint64_t *fsize;              /* per file: size when the batches were planned; a reader that meets EOF earlier writes what it got */
   uint8_t *grew;                /* per file: there are bytes behind that size -- the file is sketched alone, from all of its text */
+  const uint8_t *kind;          /* per file: 1 plain text, 2 a gzip file whose BYTES travel (its place holds them as they are) */
   bjob *jobs; int njobs;
   uint8_t *buf[BATCH_BUFS_MAX]; size_t bufcap; int nbufs;
   uint64_t *foff;               /* offset of every file inside its batch's buffer */
@@ -2329,7 +2339,8 @@ static void *breader_run(void *arg) {
     uint8_t *const place = r->buf[job->batch % r->nbufs] + r->foff[i];
     uint8_t *dst = place;
     int err = 0;
-    if (r->rows_TL) {
+    const int rows_TL = r->kind[i] == 2 ? 0 : r->rows_TL;
+    if (rows_TL) {
       if (txt_cap < r->fsize[i] + 64) {
         free(txt);
         txt_cap = (size_t)r->fsize[i] + ((size_t)1 << 20);
@@ -2360,17 +2371,17 @@ static void *breader_run(void *arg) {
       close(fd);
     }
     tr1 = now_s();
-    if (r->rows_TL && !err && r->grew[i]) r->nrows[i] = 0;
-    else if (r->rows_TL && !err) {
+    if (rows_TL && !err && r->grew[i]) r->nrows[i] = 0;
+    else if (rows_TL && !err) {
       /* the walk and the packing here, on this thread (what the file leaves free of its place is never looked at) */
       uint64_t got_rows = 0;
-      int prc = mk_fasta_pack_rows(txt, (size_t)r->fsize[i], r->rows_TL, r->rows_format, place, r->slot_rows[i], &got_rows);
+      int prc = mk_fasta_pack_rows(txt, (size_t)r->fsize[i], rows_TL, r->rows_format, place, r->slot_rows[i], &got_rows);
       if (prc == MK_ERR_ARG) { /* more rows than its place holds: into memory of its own (the batch's rows are then copied to the device) */
-        const uint64_t full = mk_fasta_pack_bound((size_t)r->fsize[i], r->rows_TL, r->rows_format);
+        const uint64_t full = mk_fasta_pack_bound((size_t)r->fsize[i], rows_TL, r->rows_format);
         void *own = NULL;
         if (posix_memalign(&own, 64, (size_t)(full ? full : 1) * MK_PACKED_PITCH) != 0) { prc = MK_ERR_NOMEM; }
         else {
-          prc = mk_fasta_pack_rows(txt, (size_t)r->fsize[i], r->rows_TL, r->rows_format, own, full, &got_rows);
+          prc = mk_fasta_pack_rows(txt, (size_t)r->fsize[i], rows_TL, r->rows_format, own, full, &got_rows);
           if (prc == MK_OK) r->priv[i] = own; else free(own);
         }
       }
@@ -2655,7 +2666,8 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--quiet")) quiet = 1;
     else if (!strcmp(argv[i], "--component-sz") && i + 1 < argc) g_component_sz = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--timing")) timing = g_timing = 1;
-    else if (!strcmp(argv[i], "--no-device-inflate")) g_no_device_inflate = 1;
+    else if (!strcmp(argv[i], "--no-device-inflate")) { g_no_device_inflate = 1; g_gz_batches = 0; }
+    else if (!strcmp(argv[i], "--device-inflate")) { g_no_device_inflate = 0; g_gz_batches = 1; }
     else if (!strcmp(argv[i], "--inflate-chunk-kib") && i + 1 < argc) g_inflate_chunk_bytes = (uint64_t)atoll(argv[++i]) << 10;
     else if (!strcmp(argv[i], "--chunk-mib") && i + 1 < argc) chunk_bytes = (uint64_t)atoi(argv[++i]) << 20;
     else if (!strcmp(argv[i], "--inflight") && i + 1 < argc) inflight = atoi(argv[++i]); /* row buffers queued for copying */
@@ -2730,7 +2742,7 @@ int main(int argc, char **argv) {
   { /* a directory of genomes goes to the device in batches of files, each file with a small table of its own: the engine's
      * hashsize-slot tables (21 GB at L2K11) are then made only if a file falls out of its batch (MK_ENGINE_LAZY_TABLES) */
     int plain = 0;
-    for (int i = 0; i < files.n; i++) plain += !is_fastq(files.v[i]) && !is_compressed(files.v[i]);
+    for (int i = 0; i < files.n; i++) plain += !is_fastq(files.v[i]) && (!is_compressed(files.v[i]) || (g_gz_batches && has_suffix(files.v[i], ".gz")));
     fut.lazy_tables = plain >= 2 && !g_no_batch && !g_host_fasta && !engines_per_gpu && !shard_files && ndev <= 1;
   }
   engine_params(&fut, &P);
@@ -2742,8 +2754,9 @@ int main(int argc, char **argv) {
   if (engines_per_gpu < 0 || engines_per_gpu > MAX_ENGINES_PER_GPU) die("--engines takes 1..%d", MAX_ENGINES_PER_GPU);
   /* which inputs can travel in batches: plain FASTA files of moderate size, when the device parses the text and one engine works */
   uint64_t *fsize = calloc((size_t)files.n, sizeof *fsize);
-  uint8_t *elig = calloc((size_t)files.n, 1);
-  if (!fsize || !elig) die("out of memory");
+  uint8_t *elig = calloc((size_t)files.n, 1); /* 1: plain text; 2: a single-member gzip file (mk_gzip_scan), inflated on the device */
+  uint32_t *gz_isize = calloc((size_t)files.n, sizeof *gz_isize);
+  if (!fsize || !elig || !gz_isize) die("out of memory");
   int n_elig = 0;
   if (files.n > 1 && !g_no_batch && !g_host_fasta && !engines_per_gpu && !shard_files && ndev <= 1) {
     if (g_batch_files < 1 || g_batch_files > (int)MK_BATCH_MAX_FILES) die("--batch-files takes 1..%u", MK_BATCH_MAX_FILES);
@@ -2759,8 +2772,19 @@ int main(int argc, char **argv) {
     if (g_batch_bytes < ((size_t)1 << 20)) g_batch_bytes = (size_t)1 << 20;
     for (int i = 0; i < files.n; i++) {
       struct stat fst;
-      if (is_fastq(files.v[i]) || is_compressed(files.v[i]) || stat(files.v[i], &fst) != 0 || !S_ISREG(fst.st_mode)) continue;
+      if (is_fastq(files.v[i]) || stat(files.v[i], &fst) != 0 || !S_ISREG(fst.st_mode)) continue;
       if (fst.st_size <= 0 || (size_t)fst.st_size > BATCH_FILE_MAX || (size_t)fst.st_size > g_batch_bytes) continue;
+      if (is_compressed(files.v[i])) { /* what genome archives ship: one gzip member.  Anything else keeps the zcat route */
+        if (!g_gz_batches || !has_suffix(files.v[i], ".gz")) continue;
+        const int fd = open(files.v[i], O_RDONLY);
+        if (fd < 0) continue;
+        mk_gzip_info gi;
+        const int grc = mk_gzip_scan(fd, NULL, (size_t)fst.st_size, &gi);
+        close(fd);
+        if (grc != MK_OK || !gi.is_single || gi.isize > BATCH_FILE_MAX || gi.isize > g_batch_bytes) continue;
+        fsize[i] = (uint64_t)fst.st_size; gz_isize[i] = gi.isize; elig[i] = 2; n_elig++;
+        continue;
+      }
       fsize[i] = (uint64_t)fst.st_size; elig[i] = 1; n_elig++;
     }
     /* test hook (tests/test_golden.py): MK_TEST_PLAN_SKEW="<m>:<d>" plans every m-th file with a size off by d bytes, i.e. as if
@@ -2858,7 +2882,8 @@ int main(int argc, char **argv) {
     const uint32_t rows_format = g_batch_narrow ? MK_ROWS_PACKED : MK_ROWS_WIDE;
     uint64_t *slot_rows = calloc((size_t)files.n, sizeof *slot_rows), *nrows_of = calloc((size_t)files.n, sizeof *nrows_of);
     uint8_t **priv = calloc((size_t)files.n, sizeof *priv);
-    if (!jobs || !foff || !left || !failed || !slot_rows || !nrows_of || !priv || !grew) die("out of memory");
+    int *gzpos = calloc((size_t)files.n, sizeof *gzpos); /* a gzip file's index in the batch the engine got, -1: it does not travel in it */
+    if (!jobs || !foff || !left || !failed || !slot_rows || !nrows_of || !priv || !grew || !gzpos) die("out of memory");
     int njobs = 0, nbatches = 0;
     size_t bufcap = 0;
     for (int i = 0; i < files.n;) {
@@ -2866,25 +2891,27 @@ int main(int argc, char **argv) {
       size_t at = 0;
       int n = 0;
       size_t text_at = 0;
-      while (i + n < files.n && elig[i + n] && n < g_batch_files && (n == 0 || text_at + fsize[i + n] <= g_batch_bytes)) {
+      const int gz = elig[i] == 2; /* a batch holds files of one kind; its budget is counted in TEXT bytes either way */
+      while (i + n < files.n && elig[i + n] == elig[i] && n < g_batch_files && (n == 0 || text_at + (gz ? gz_isize[i + n] : fsize[i + n]) <= g_batch_bytes)) {
         foff[i + n] = at;
-        if (batch_rows) { /* its place: the rows its text can give at most */
+        if (gz) at += ((size_t)fsize[i + n] + 1023u) & ~(size_t)1023u; /* the file's bytes as they are */
+        else if (batch_rows) { /* its place: the rows its text can give at most */
           /* (wide rows: an extension row for one row in sixteen -- a genome has them at contig ends and runs of N; a file with
            * more gets memory of its own, breader_run) */
           const uint64_t full = mk_fasta_pack_bound((size_t)fsize[i + n], P.TL, rows_format);
           slot_rows[i + n] = rows_format == MK_ROWS_WIDE ? full / 2u + full / 32u + 8u : full;
           at += (size_t)slot_rows[i + n] * MK_PACKED_PITCH;
         } else at += ((size_t)fsize[i + n] + 1023u) & ~(size_t)1023u;
-        text_at += ((size_t)fsize[i + n] + 1023u) & ~(size_t)1023u;
+        text_at += ((size_t)(gz ? gz_isize[i + n] : fsize[i + n]) + 1023u) & ~(size_t)1023u;
         n++;
       }
       if (at > bufcap) bufcap = at;
-      jobs[njobs].first = i; jobs[njobs].n = n; jobs[njobs].batch = nbatches++; left[njobs] = n; njobs++;
+      jobs[njobs].first = i; jobs[njobs].n = n; jobs[njobs].batch = nbatches++; jobs[njobs].gz = gz; left[njobs] = n; njobs++;
       i += n;
     }
     breader br;
     memset(&br, 0, sizeof br);
-    br.files = &files; br.fsize = fsize; br.grew = grew; br.jobs = jobs; br.njobs = njobs; br.foff = foff; br.left = left; br.failed = failed;
+    br.files = &files; br.fsize = fsize; br.grew = grew; br.kind = elig; br.jobs = jobs; br.njobs = njobs; br.foff = foff; br.left = left; br.failed = failed;
     br.rows_TL = batch_rows ? P.TL : 0; br.rows_format = rows_format; br.slot_rows = slot_rows; br.nrows = nrows_of; br.priv = priv;
     br.bufcap = (bufcap + 4096 + (((size_t)2 << 20) - 1)) & ~(((size_t)2 << 20) - 1); /* whole 2 MiB granules: every buffer is pinned on its own */
     pthread_mutex_init(&br.mu, NULL);
@@ -2925,18 +2952,26 @@ int main(int argc, char **argv) {
     const int mode = uniq ? MK_MODE_UNIQ_SET : MK_MODE_SET;
     mk_batch_file *bf = calloc((size_t)g_batch_files, sizeof *bf);
     mk_batch_result *bres = calloc((size_t)g_batch_files, sizeof *bres);
-    if (!bf || !bres) die("out of memory");
+    mk_gz_file *gzf = calloc((size_t)g_batch_files, sizeof *gzf);
+    uint32_t *gzst = calloc((size_t)g_batch_files, sizeof *gzst);
+    if (!bf || !bres || !gzf || !gzst) die("out of memory");
     int fly[2], nfly = 0, done_files = 0;
     const int btrace = getenv("MK_BATCH_TRACE") != NULL;
     #define BATCH_END_OLDEST() do { \
       const bjob *bj_ = &jobs[fly[0]]; \
       const double tf_ = now_s(); \
-      rc = mk_sketch_batch_end(c.eng, bres); \
+      rc = bj_->nsub ? mk_sketch_batch_end(c.eng, bres) : MK_OK; /* (nsub == 0: every file of a gzip batch changed on disk) */ \
       t_finish += now_s() - tf_; \
       if (btrace) fprintf(stderr, "[batch %d] end: called %.3f returned %.3f ms\n", bj_->batch, (tf_ - g_t0) * 1e3, (now_s() - g_t0) * 1e3); \
       if (rc != MK_OK) die("mk_sketch_batch_end failed (%d): %s", rc, mk_last_error(c.eng)); \
+      if (bj_->gz && bj_->nsub) (void)mk_sketch_batch_gz_status(c.eng, gzst, (uint32_t)bj_->nsub); \
       for (int k_ = 0; k_ < bj_->n; k_++) { \
         const char *path_ = files.v[bj_->first + k_]; \
+        const int p_ = bj_->gz ? gzpos[bj_->first + k_] : k_; /* its result in bres */ \
+        /* a gzip file the device route gave up with a status (more members behind the first, damage): again through zcat, which alone \
+         * decides whether the file is damaged -- with the messages and the exit status it has always had */ \
+        const int gzfall_ = bj_->gz && p_ >= 0 && gzst[p_] != 0; \
+        if (gzfall_) { grew[bj_->first + k_] = 1; g_gz_fallback = mk_inflate_status_text((int)gzst[p_]); } \
         if (priv[bj_->first + k_]) { free(priv[bj_->first + k_]); priv[bj_->first + k_] = NULL; } \
         if (grew[bj_->first + k_]) { /* longer than its place: alone, from the whole file, where it stands in the order */ \
           mk_result res_; \
@@ -2944,13 +2979,20 @@ int main(int argc, char **argv) {
           rc = mk_sketchdir_add(sd, path_, &res_); \
           if (rc != MK_OK) die("writing sketch for %s failed (%d)", path_, rc); \
           mk_result_release(c.eng, &res_); \
+          g_gz_fallback = NULL; \
           if (!quiet) printf("%d/%d decomposing %s\r", ++done_files, files.n, path_); \
           continue; \
         } \
-        if (bres[k_].status == MK_ERR_CROWDED) die("the context space is too crowd, try rerun the program using -k%d", P.k + 1); \
-        if (bres[k_].status == MK_ERR_FORMAT) die("fasta2co(): can not find seqences head start from '>' 0 (%s ends inside a header line)", path_); \
-        if (bres[k_].status != MK_OK) die("sketching %s failed (%d)", path_, bres[k_].status); \
-        rc = mk_sketchdir_add(sd, path_, &bres[k_].r); \
+        if (bj_->gz) { \
+          mk_bgzf_stats gs_; \
+          memset(&gs_, 0, sizeof gs_); \
+          gs_.blocks = 1; gs_.chunks = 1; gs_.comp_bytes = fsize[bj_->first + k_]; gs_.text_bytes = gz_isize[bj_->first + k_]; \
+          report_route(path_, "device-inflate", &gs_); \
+        } \
+        if (bres[p_].status == MK_ERR_CROWDED) die("the context space is too crowd, try rerun the program using -k%d", P.k + 1); \
+        if (bres[p_].status == MK_ERR_FORMAT) die("fasta2co(): can not find seqences head start from '>' 0 (%s ends inside a header line)", path_); \
+        if (bres[p_].status != MK_OK) die("sketching %s failed (%d)", path_, bres[p_].status); \
+        rc = mk_sketchdir_add(sd, path_, &bres[p_].r); \
         if (rc != MK_OK) die("writing sketch for %s failed (%d)", path_, rc); \
         if (!quiet) printf("%d/%d decomposing %s\r", ++done_files, files.n, path_); \
       } \
@@ -2977,7 +3019,21 @@ int main(int argc, char **argv) {
         pthread_mutex_unlock(&br.mu);
         t_batch_wait_read += now_s() - tw;
       }
-      for (int k = 0; k < bj->n; k++) {
+      int nsub = bj->n;
+      if (bj->gz) nsub = 0;
+      for (int k = 0; k < bj->n && bj->gz; k++) { /* the bytes the readers got, looked at again: a file that changed since it was planned is sketched alone */
+        const int i = bj->first + k;
+        gzpos[i] = -1;
+        if (failed[i]) die("%s: %s", files.v[i], strerror(failed[i]));
+        if (grew[i]) continue;
+        mk_gzip_info gi;
+        uint8_t *at = br.buf[bj->batch % nbufs] + foff[i];
+        if (mk_gzip_scan(-1, at, (size_t)fsize[i], &gi) != MK_OK || !gi.is_single || gi.isize != gz_isize[i]) { grew[i] = 1; continue; }
+        gzf[nsub].comp = at; gzf[nsub].n = fsize[i]; gzf[nsub].info = gi;
+        gzpos[i] = nsub++;
+      }
+      jobs[j].nsub = nsub;
+      for (int k = 0; k < bj->n && !bj->gz; k++) {
         const int i = bj->first + k;
         if (failed[i] == -MK_ERR_FORMAT + 100000) die("fasta2co(): can not find seqences head start from '>' 0 (%s ends inside a header line)", files.v[i]);
         if (failed[i]) die("%s: %s", files.v[i], strerror(failed[i]));
@@ -2997,7 +3053,8 @@ int main(int argc, char **argv) {
       if (c.t_first_push == 0) c.t_first_push = now_s() - g_t0;
       {
         const double tb = now_s();
-        rc = batch_rows ? mk_sketch_batch_begin_rows(c.eng, mode, rows_format, bf, (uint32_t)bj->n) : mk_sketch_batch_begin(c.eng, mode, bf, (uint32_t)bj->n);
+        if (bj->gz) rc = nsub ? mk_sketch_batch_begin_gz(c.eng, mode, gzf, (uint32_t)nsub) : MK_OK;
+        else rc = batch_rows ? mk_sketch_batch_begin_rows(c.eng, mode, rows_format, bf, (uint32_t)bj->n) : mk_sketch_batch_begin(c.eng, mode, bf, (uint32_t)bj->n);
         t_batch_begin += now_s() - tb;
         nbatches_done++;
         if (btrace) fprintf(stderr, "[batch %d] begin: called %.3f returned %.3f ms\n", bj->batch, (tb - g_t0) * 1e3, (now_s() - g_t0) * 1e3);

@@ -95,6 +95,7 @@ const char *mk_inflate_status_text(int status) {
     case MK_INFL_INPUT: return "compressed data exhausted";
     case MK_INFL_OUTPUT_LEN: return "output length not equal to ISIZE";
     case MK_INFL_CRC: return "CRC mismatch";
+    case MK_INFL_TRAILING: return "more members behind the first";
     default: return "unknown status";
   }
 }

@@ -143,6 +143,17 @@ __global__ void __launch_bounds__(256) mk_fab_emit_kernel(const uint8_t *text, c
   for (uint64_t i = g0 + lane; i < g1; i += 64u) p[i] = (uint8_t)'\n';
 }
 
+/* mk_sketch_batch_begin_gz, behind the clear and in front of the walk, one thread per file: the file's inflate status (MK_INFL_*,
+ * metakssd_hip.h) goes home in its mk_bstat; a file with a status other than 0 keeps no text -- what lies in its place is never
+ * read as FASTA, its region of the stream is filled with '\n' like an empty file's */
+__global__ void __launch_bounds__(256) mk_b_gz_status_kernel(const mk_batch_dev b, const uint32_t *gz_status) {
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= b.nfiles) return;
+  const uint32_t st = gz_status[f];
+  b.stat[f].pad[0] = st;
+  if (st) const_cast<mk_bfile *>(b.files)[f].text_len = 0ull;
+}
+
 /* ---- a candidate's file and its table ---------------------------------------------------------------------------------------
  * counted upsert into the table of the file that row `row` belongs to: linear probing from a multiplicative hash (the order of
  * the key list does not matter here: the layout is made from ordinals), same slot format and the same commutative updates as

@@ -10,6 +10,7 @@
 #include "mk_kernels.hip.h"
 #include "mk_stream.hip.h"
 #include "mk_batch.hip.h"
+#include "mk_gz.hip.h"
 #include "mk_packed.hip.h"
 
 #include <math.h>
@@ -143,6 +144,7 @@ struct mk_engine {
   struct mk_bctx *bctx[3] = {nullptr, nullptr, nullptr};
   uint64_t batch_begun = 0, batch_ended = 0;
   int batch_tb_opt = 0;                /* MK_OPT_BATCH_TAB_BITS: 0 = by the largest file of the batch */
+  std::vector<uint32_t> gz_status;     /* MK_INFL_* per file of the batch mk_sketch_batch_end handed out last (mk_sketch_batch_gz_status) */
   const mk_batch_dev *cur_batch = nullptr; /* set around the scan launches of a batch */
 
   int mode = -1;
@@ -2146,6 +2148,11 @@ extern "C" int mk_synth_rows_device(int device, void *hip_stream, uint64_t seed,
 struct mk_dbuf { void *p = nullptr; size_t cap = 0; };
 struct mk_bctx {
   mk_dbuf text, stream, sum, desc, zero, map, list, bcur;
+  mk_dbuf comp, gztab, gzwork;                     /* mk_sketch_batch_begin_gz: compressed bytes, member table, statuses and slice CRCs */
+  void *h_comp = nullptr; size_t h_comp_cap = 0;   /* pinned: the compressed bytes of files that do not lie in one stretch */
+  void *h_gztab = nullptr; size_t h_gztab_cap = 0; /* pinned: the member table */
+  bool gz = false;                                 /* the texts were made on the device: a file sketched alone fetches its text from there */
+  std::vector<uint64_t> text_off;                  /* per file of a gz batch: its place in `text` */
   void *h_desc = nullptr; size_t h_desc_cap = 0;   /* pinned: what goes up in one small copy (descriptor, files, seg0s, row0s) */
   void *h_stat = nullptr; size_t h_stat_cap = 0;   /* pinned: what comes back first (per-file status, per-component sizes, totals) */
   uint32_t *h_ids = nullptr; size_t h_ids_cap = 0; /* pinned: the ids */
@@ -2185,7 +2192,9 @@ static int mk_pinned_fit(mk_engine *e, void **p, size_t *cap, size_t need) {
 }
 static void mk_bctx_free(mk_bctx *c) {
   if (!c) return;
-  for (mk_dbuf *b : {&c->text, &c->stream, &c->sum, &c->desc, &c->zero, &c->map, &c->list, &c->bcur}) hipFree(b->p);
+  for (mk_dbuf *b : {&c->text, &c->stream, &c->sum, &c->desc, &c->zero, &c->map, &c->list, &c->bcur, &c->comp, &c->gztab, &c->gzwork}) hipFree(b->p);
+  if (c->h_comp) hipHostFree(c->h_comp);
+  if (c->h_gztab) hipHostFree(c->h_gztab);
   if (c->h_desc) hipHostFree(c->h_desc);
   if (c->h_stat) hipHostFree(c->h_stat);
   if (c->h_ids) hipHostFree(c->h_ids);
@@ -2214,7 +2223,9 @@ static uint64_t mk_rows_per_launch(const mk_engine *e, uint32_t row_bases, int t
  * no mk_fab_* kernels; where the rows lie in ONE stretch of pinned memory the scan kernel reads them THERE, through the mapping
  * (profiles/r04_probe_hostread.jsonl: a kernel reads registered host memory at 55.5 GB/s, the copy engine moves it at 57.0 and costs 7.7 ms
  * of set-up at the first copy of a process) */
-static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *files, uint32_t nfiles, const uint32_t format) {
+/* gz != nullptr: the texts are made on the device from single-member gzip files (mk_sketch_batch_begin_gz); files[i].n is then the
+ * text's size, the trailer's ISIZE, and files[i].text is not used */
+static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *files, uint32_t nfiles, const uint32_t format, const mk_gz_file *gz = nullptr) {
   if (!e || !files) return MK_ERR_ARG;
   if (format != 0u && format != MK_ROWS_PACKED && format != MK_ROWS_WIDE) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_rows: format MK_ROWS_PACKED or MK_ROWS_WIDE");
   const bool rows = format != 0u;
@@ -2228,7 +2239,7 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
   if (rows && !mk_params_packed_ok(&e->P)) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_rows: no scan kernel for packed rows at k %d, subk %d", e->P.k, e->P.subk);
   uint64_t total = 0, nmax = 0;
   for (uint32_t i = 0; i < nfiles; i++) {
-    if (!files[i].text && files[i].n) return MK_ERR_ARG;
+    if (!gz && !files[i].text && files[i].n) return MK_ERR_ARG;
     if (rows && ((files[i].n % MK_PACKED_PITCH) || ((uintptr_t)files[i].text & 15u))) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_rows: file %u: rows of 64 bytes, 16-byte aligned", i);
     if (files[i].n > MK_BATCH_FILE_MAX) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin: file %u has %llu bytes (at most %llu)", i, (unsigned long long)files[i].n, (unsigned long long)MK_BATCH_FILE_MAX);
     total += files[i].n;
@@ -2250,7 +2261,7 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
    * Rows: read where they lie when they are in ascending order, 64 bytes apart, inside memory the device has mapped (both ends are
    * asked for: what lies between two files is never touched, but it must be the caller's ONE pinned stretch); anything else --
    * separate arrays that merely happen to lie in ascending order, pageable memory -- is copied file by file. */
-  bool one_copy = true;
+  bool one_copy = !gz; /* (gz: every text goes to a place of its own in the device's buffer) */
   const uint8_t *rows_dev = nullptr;
   for (uint32_t i = 1; i < nfiles && one_copy; i++) {
     if (rows) {
@@ -2311,6 +2322,25 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
     hseg0[i] = f.seg0;
     hrow0[i] = f.row0;
   }
+  /* ---- gz: where the compressed bytes lie on the device.  One copy from where they are when every file starts where the one in
+   * front of it ends, rounded up to 1 KiB, the first at a 16-byte boundary (a reader's buffer filled file by file: they must then stay
+   * untouched until the batch's end); anything else is packed into pinned staging here */
+  bool comp_in_place = gz != nullptr;
+  uint64_t comp_span = 0;
+  uint32_t nslices = 0;
+  std::vector<uint64_t> coff;
+  if (gz) {
+    coff.assign(nfiles, 0);
+    if ((uintptr_t)gz[0].comp & 15u) comp_in_place = false;
+    for (uint32_t i = 1; i < nfiles && comp_in_place; i++)
+      if (gz[i].comp != gz[i - 1].comp + ((gz[i - 1].n + 1023u) & ~(uint64_t)1023u)) comp_in_place = false;
+    for (uint32_t i = 0; i < nfiles; i++) {
+      coff[i] = comp_in_place ? (uint64_t)(gz[i].comp - gz[0].comp) : comp_span;
+      comp_span = coff[i] + (comp_in_place ? gz[i].n : ((gz[i].n + 15u) & ~(uint64_t)15u));
+      nslices += mk_gz_slices(gz[i].info.isize);
+    }
+    if (comp_span >= (1ull << 31)) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_gz: %llu compressed bytes (below 2 GiB a batch)", (unsigned long long)comp_span);
+  }
   const uint64_t text_span = rows ? 0 : one_copy ? (uint64_t)(files[nfiles - 1].text - files[0].text) + files[nfiles - 1].n : toff;
   const uint64_t total_rows = soff / (rows ? MK_PACKED_PITCH : pitch);
   const uint32_t nseg_total = seg;
@@ -2359,6 +2389,26 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
   if ((rc = mk_dbuf_fit(e, c->list, (size_t)N * 40))) return rc;
   if ((rc = mk_dbuf_fit(e, c->bcur, (size_t)nb * 4 + 16))) return rc;
   if ((rc = mk_pinned_fit(e, &c->h_stat, &c->h_stat_cap, c->stat_bytes))) return rc;
+  if (gz) {
+    if ((rc = mk_dbuf_fit(e, c->comp, (size_t)comp_span + 64))) return rc;
+    if ((rc = mk_dbuf_fit(e, c->gztab, mk_gz_table_bytes(nfiles)))) return rc;
+    if ((rc = mk_dbuf_fit(e, c->gzwork, mk_gz_work_words(nfiles, nslices) * 4))) return rc;
+    if ((rc = mk_pinned_fit(e, &c->h_gztab, &c->h_gztab_cap, mk_gz_table_bytes(nfiles)))) return rc;
+    if (!comp_in_place && (rc = mk_pinned_fit(e, &c->h_comp, &c->h_comp_cap, (size_t)comp_span + 64))) return rc;
+    mk_infl_blk *tab = (mk_infl_blk *)c->h_gztab;
+    uint32_t *slice0s = (uint32_t *)((uint8_t *)c->h_gztab + mk_gz_slice0_at(nfiles));
+    uint32_t s0 = 0;
+    c->text_off.assign(nfiles, 0);
+    for (uint32_t i = 0; i < nfiles; i++) {
+      const mk_gzip_info &gi = gz[i].info;
+      tab[i] = mk_infl_blk{(uint32_t)(coff[i] + gi.pay_off), (uint32_t)gi.pay_len, (uint32_t)hf[i].text_off, gi.isize, gi.crc32};
+      slice0s[i] = s0;
+      s0 += mk_gz_slices(gi.isize);
+      c->text_off[i] = hf[i].text_off;
+      if (!comp_in_place) memcpy((uint8_t *)c->h_comp + coff[i], gz[i].comp, (size_t)gz[i].n);
+    }
+    slice0s[nfiles] = s0;
+  }
   const double tr1 = trace ? mk_tick_now() : 0.0;
   {
     uint8_t *z = (uint8_t *)c->zero.p;
@@ -2394,6 +2444,7 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
   }
   c->hb = *hb;
   c->mode = mode; c->nfiles = nfiles; c->rows = rows; c->format = format; c->rows_src = rows ? (rows_dev ? rows_dev : (const uint8_t *)c->stream.p) : nullptr;
+  c->gz = gz != nullptr;
   c->files.assign(files, files + nfiles);
   const mk_batch_dev *dbatch = (const mk_batch_dev *)dd;
   hipStream_t s = e->stream;
@@ -2417,6 +2468,9 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
     if (!rows_dev) /* (not one mapped stretch: file by file, side by side) */
       for (uint32_t i = 0; i < nfiles; i++)
         if (files[i].n) MK_HIP(e, hipMemcpyAsync((uint8_t *)c->stream.p + hf[i].stream_off, files[i].text, (size_t)files[i].n, hipMemcpyHostToDevice, s));
+  } else if (gz) {
+    MK_HIP(e, hipMemcpyAsync(c->comp.p, comp_in_place ? (const void *)gz[0].comp : (const void *)c->h_comp, (size_t)comp_span, hipMemcpyHostToDevice, s));
+    MK_HIP(e, hipMemcpyAsync(c->gztab.p, c->h_gztab, mk_gz_table_bytes(nfiles), hipMemcpyHostToDevice, s));
   } else if (one_copy) {
     if (text_span) MK_HIP(e, hipMemcpyAsync(c->text.p, files[0].text, (size_t)text_span, hipMemcpyHostToDevice, s));
   } else {
@@ -2427,6 +2481,10 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
   const unsigned wide = (unsigned)e->num_cu * 8u;
   hipLaunchKernelGGL(mk_b_clear_kernel, dim3(wide), dim3(256), 0, s, (uint4 *)c->zero.p, (unsigned long long)(zero_bytes / 16u), (uint4 *)c->map.p,
                      (unsigned long long)(N / 2u), (uint4 *)nullptr, 0ull);
+  if (gz) { /* the texts: inflate, CRC; a file with a status keeps no text (behind the clear: the status travels in the file's mk_bstat) */
+    MK_HIP(e, mk_gz_launch(s, (const uint8_t *)c->comp.p, c->gztab.p, nfiles, nslices, (uint8_t *)c->text.p, (uint32_t *)c->gzwork.p));
+    hipLaunchKernelGGL(mk_b_gz_status_kernel, dim3((nfiles + 255u) / 256u), dim3(256), 0, s, c->hb, (const uint32_t *)c->gzwork.p);
+  }
   if (!rows) {
     hipLaunchKernelGGL(mk_fab_summary_kernel, dim3((nseg_total + 3u) / 4u), dim3(256), 0, s, (const uint8_t *)c->text.p, c->hb, nseg_total, (mk_fa_sum *)c->sum.p);
     hipLaunchKernelGGL(mk_fab_scan_kernel, dim3(nfiles), dim3(1024), 0, s, (mk_fa_sum *)c->sum.p, c->hb, TL, pitch);
@@ -2486,6 +2544,26 @@ extern "C" int mk_sketch_batch_begin_rows(mk_engine *e, int mode, uint32_t forma
   return mk_batch_begin_impl(e, mode, files, nfiles, format);
 }
 
+extern "C" int mk_sketch_batch_begin_gz(mk_engine *e, int mode, const mk_gz_file *files, uint32_t nfiles) {
+  if (!e || !files) return MK_ERR_ARG;
+  if (e->scan_stream) return mk_fail(e, MK_ERR_STATE, "mk_sketch_batch_begin_gz: MK_OPT_SPLIT_CUS runs the scan on a queue of its own");
+  if (nfiles < 1 || nfiles > MK_BATCH_MAX_FILES) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_gz: 1 .. %u files", MK_BATCH_MAX_FILES);
+  std::vector<mk_batch_file> texts(nfiles);
+  for (uint32_t i = 0; i < nfiles; i++) {
+    const mk_gzip_info &gi = files[i].info;
+    if (!files[i].comp || !gi.is_single || gi.isize < 1u || gi.pay_len < 1u || gi.pay_len >= (1ull << 31) || gi.pay_off + gi.pay_len + 8u > files[i].n)
+      return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_gz: file %u: not what mk_gzip_scan accepts", i);
+    texts[i] = mk_batch_file{nullptr, gi.isize};
+  }
+  return mk_batch_begin_impl(e, mode, texts.data(), nfiles, 0u, files);
+}
+
+extern "C" int mk_sketch_batch_gz_status(mk_engine *e, uint32_t *status, uint32_t nfiles) {
+  if (!e || (!status && nfiles)) return MK_ERR_ARG;
+  for (uint32_t i = 0; i < nfiles; i++) status[i] = i < e->gz_status.size() ? e->gz_status[i] : 0u;
+  return MK_OK;
+}
+
 extern "C" int mk_sketch_batch_end(mk_engine *e, mk_batch_result *out) {
   if (!e || !out) return MK_ERR_ARG;
   if (e->batch_begun == e->batch_ended) return mk_fail(e, MK_ERR_STATE, "mk_sketch_batch_end without a batch in flight");
@@ -2518,13 +2596,16 @@ extern "C" int mk_sketch_batch_end(mk_engine *e, mk_batch_result *out) {
   c->alone_ids.clear();
   /* files the batch could not take: alone, through the ordinary path (their sketches are the same either way) */
   size_t n_alone = 0;
+  e->gz_status.assign(nfiles, 0u);
+  for (uint32_t i = 0; i < nfiles && c->gz; i++) e->gz_status[i] = st[i].pad[0];
+  std::vector<uint8_t> gz_text; /* a gz batch's file that is sketched alone: its text comes back from the device first */
   for (uint32_t i = 0; i < nfiles; i++) if ((st[i].flags & MK_BF_REDO) && !(st[i].flags & MK_BF_HEADER_END)) n_alone++;
   c->alone_ids.resize(n_alone);
   size_t ai = 0;
   for (uint32_t i = 0; i < nfiles; i++) {
     out[i].status = MK_OK; out[i].alone = 0;
     out[i].r.component_num = (int32_t)C; out[i].r.total = 0; out[i].r.components = c->comps.data() + (size_t)i * C;
-    if (st[i].flags & MK_BF_HEADER_END) { out[i].status = MK_ERR_FORMAT; continue; }
+    if (e->gz_status[i] || (st[i].flags & MK_BF_HEADER_END)) { out[i].status = MK_ERR_FORMAT; continue; }
     if (!(st[i].flags & MK_BF_REDO)) continue;
     out[i].alone = 1;
     mk_result r;
@@ -2535,6 +2616,12 @@ extern "C" int mk_sketch_batch_end(mk_engine *e, mk_batch_result *out) {
       for (uint64_t done = 0; done < nr && rc == MK_OK; done += per)
         rc = mk_launch_scan_ex(e, c->rows_src + c->row_off[i] + done * MK_PACKED_PITCH, MK_PACKED_PITCH | c->format, MK_PACKED_PITCH | c->format, 0u,
                                nr - done < per ? nr - done : per, nullptr, done);
+    } else if (rc == MK_OK && c->gz) {
+      gz_text.resize((size_t)c->files[i].n);
+      hipError_t hr = hipMemcpyAsync(gz_text.data(), (const uint8_t *)c->text.p + c->text_off[i], gz_text.size(), hipMemcpyDeviceToHost, c->used_stream);
+      if (hr == hipSuccess) hr = hipStreamSynchronize(c->used_stream);
+      if (hr != hipSuccess) { mk_result dummy; (void)mk_sketch_finish(e, &dummy); return mk_fail(e, MK_ERR_HIP, "batch: fetching a file's text: %s", hipGetErrorString(hr)); }
+      rc = mk_sketch_push_stream(e, gz_text.data(), gz_text.size(), 1);
     } else if (rc == MK_OK) rc = mk_sketch_push_stream(e, c->files[i].text, c->files[i].n, 1);
     if (rc == MK_OK) rc = mk_sketch_finish(e, &r);
     else if (e->begun) { mk_result dummy; (void)mk_sketch_finish(e, &dummy); }

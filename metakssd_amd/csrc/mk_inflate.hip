@@ -47,6 +47,7 @@
 #include <unistd.h>
 
 #include "metakssd_hip.h"
+#include "mk_gz.hip.h"
 
 #define MK_INFL_WAVES 4u
 #define MK_INFL_WIN 1024u      /* bytes of the compressed stream a wave holds in LDS */
@@ -58,8 +59,6 @@
 #define MK_FQ_LINE_MAX 4096u   /* MK_FQ_LEN: a line of this many bytes with its '\n' is refused (mk_frontend.c) */
 
 namespace {
-
-struct mk_infl_blk { uint32_t pay_off, pay_len, out_off, isize, crc; };
 
 struct mk_fq_res {
   uint32_t nl, nrec, consumed, maxline, maxseq; /* text coordinates */
@@ -200,6 +199,51 @@ __device__ int mk_build(const uint8_t *lens, uint32_t n, uint16_t *cnt, uint16_t
   return 0;
 }
 
+/* The CRC register after the n >= 1 bytes at p, started from zero (ones: from all ones, n >= 4 then -- the start value is the
+ * first four bytes complemented), by the whole wave: every lane runs the byte table over an equal slice (the bytes are thought
+ * padded with zero bytes IN FRONT, which a zero register ignores), the 64 registers are folded with the 32x32 GF(2) matrix
+ * "advance by one slice", squared at every level.  mat: 32 words of the wave's LDS.  The same value in every lane. */
+__device__ __forceinline__ uint32_t mk_crc_wave(const uint8_t *p, uint32_t n, const uint32_t *crctab, uint32_t *mat, uint32_t lane, bool ones) {
+  const uint32_t SL = (n + 63u) / 64u, pad = 64u * SL - n;
+  uint32_t r = 0;
+  for (uint32_t k = 0; k < SL; k++) {
+    const uint32_t q = lane * SL + k;
+    if (q >= pad) {
+      const uint32_t idx = q - pad;
+      uint32_t v = p[idx];
+      if (ones && idx < 4u) v ^= 0xffu;
+      r = crctab[(r ^ v) & 0xffu] ^ (r >> 8);
+    }
+  }
+  { /* column j of "advance by SL zero bytes" */
+    uint32_t m = 1u << (lane & 31u);
+    for (uint32_t k = 0; k < SL; k++) m = crctab[m & 0xffu] ^ (m >> 8);
+    mk_lds_fence();
+    if (lane < 32u) mat[lane] = m;
+    mk_lds_fence();
+  }
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    uint32_t t = 0, col = 0;
+    const uint32_t mine = mat[lane & 31u];
+    for (uint32_t bit = 0; bit < 32u; bit++) {
+      const uint32_t mb = mat[bit];
+      if ((r >> bit) & 1u) t ^= mb;
+      if ((mine >> bit) & 1u) col ^= mb;
+    }
+    const uint32_t u = (uint32_t)__shfl_up((int)t, d);
+    if ((lane & (2u * d - 1u)) == 2u * d - 1u) r ^= u;
+    mk_lds_fence();
+    if (lane < 32u) mat[lane] = col; /* the matrix squared: twice the distance at the next level */
+    mk_lds_fence();
+  }
+  return (uint32_t)__shfl((int)r, 63);
+}
+
+/* GZ: a plain gzip member of any size (mk_inflate_members, mk_sketch_batch_begin_gz).  No CRC on this wave -- mk_crc32_files_kernel
+ * spreads it over the device --, a final block that ends before the payload is MK_INFL_TRAILING, and work[] (mk_gz.hip.h) takes
+ * the bytes consumed and written beside the status.  Positions are 32-bit: a payload is below 2^31 bytes, a text at most
+ * MK_BATCH_FILE_MAX, pos never passes isize + 258 before it is tested against it. */
+template <bool GZ>
 __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_inflate_kernel(const uint8_t *__restrict__ comp, const mk_infl_blk *__restrict__ blks,
                                                                          uint32_t nblocks, uint8_t *text, uint32_t *status) {
   __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
@@ -338,6 +382,15 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_inflate_kernel(const ui
   } while (!last);
   if (!st && !flush()) st = MK_INFL_OUTPUT_LEN;
   if (!st && b.past_end()) st = MK_INFL_INPUT;
+  if (GZ) {
+    uint64_t used = (b.bitpos() + 7u) >> 3;
+    if (used > b.end) used = b.end;
+    const uint32_t consumed = (uint32_t)used - shift;
+    if (!st && consumed < mk_uni(B.pay_len)) st = MK_INFL_TRAILING;
+    if (!st && pos != isize) st = MK_INFL_OUTPUT_LEN;
+    if (lane == 0u) { status[blk] = st; status[nblocks + blk] = consumed; status[2u * nblocks + blk] = pos; }
+    return;
+  }
   if (!st && pos != isize) st = MK_INFL_OUTPUT_LEN;
 
   if (!st) { /* CRC32 of out[0, isize) */
@@ -348,43 +401,75 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_inflate_kernel(const ui
       for (uint32_t i = 0; i < isize; i++) c = crctab[(c ^ out[i]) & 0xffu] ^ (c >> 8);
       crc = ~c;
     } else {
-      const uint32_t SL = (isize + 63u) / 64u, pad = 64u * SL - isize;
-      uint32_t r = 0;
-      for (uint32_t k = 0; k < SL; k++) {
-        const uint32_t p = lane * SL + k;
-        if (p >= pad) {
-          const uint32_t idx = p - pad;
-          uint32_t v = out[idx];
-          if (idx < 4u) v ^= 0xffu;
-          r = crctab[(r ^ v) & 0xffu] ^ (r >> 8);
-        }
-      }
-      { /* column j of "advance by SL zero bytes" */
-        uint32_t m = 1u << (lane & 31u);
-        for (uint32_t k = 0; k < SL; k++) m = crctab[m & 0xffu] ^ (m >> 8);
-        mk_lds_fence();
-        if (lane < 32u) L.mat[lane] = m;
-        mk_lds_fence();
-      }
-      for (uint32_t d = 1; d < 64u; d <<= 1) {
-        uint32_t t = 0, col = 0;
-        const uint32_t mine = L.mat[lane & 31u];
-        for (uint32_t bit = 0; bit < 32u; bit++) {
-          const uint32_t mb = L.mat[bit];
-          if ((r >> bit) & 1u) t ^= mb;
-          if ((mine >> bit) & 1u) col ^= mb;
-        }
-        const uint32_t u = (uint32_t)__shfl_up((int)t, d);
-        if ((lane & (2u * d - 1u)) == 2u * d - 1u) r ^= u;
-        mk_lds_fence();
-        if (lane < 32u) L.mat[lane] = col; /* the matrix squared: twice the distance at the next level */
-        mk_lds_fence();
-      }
-      crc = ~(uint32_t)__shfl((int)r, 63);
+      crc = ~mk_crc_wave(out, isize, crctab, L.mat, lane, true);
     }
     if (crc != mk_uni(B.crc)) st = MK_INFL_CRC;
   }
   if (lane == 0u) status[blk] = st;
+}
+
+/* ---- CRC32 of many texts, many waves per text -------------------------------------------------------------------------------------
+ * Slice s of the launch is slice s - slice0s[f] of member f: MK_CRC_SLICE bytes of its text (the last one what is left), one wave.
+ * What it leaves is the register started from ZERO: registers of neighbouring slices combine linearly. */
+__global__ void __launch_bounds__(256) mk_crc32_files_kernel(const uint8_t *__restrict__ text, const mk_infl_blk *__restrict__ blks, const uint32_t *__restrict__ slice0s,
+                                                             uint32_t nfiles, uint32_t nslices, uint32_t *slice_crc) {
+  __shared__ uint32_t crctab[256];
+  __shared__ uint32_t mat[4][32];
+  {
+    uint32_t c = threadIdx.x;
+    for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+    crctab[threadIdx.x] = c;
+  }
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t s = blockIdx.x * 4u + wave;
+  if (s >= nslices) return;
+  uint32_t lo = 0, hi = nfiles; /* the last member whose first slice is <= s (members without text share their successor's) */
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (slice0s[mid] <= s) lo = mid; else hi = mid;
+  }
+  const uint32_t f = lo;
+  const uint32_t isize = mk_uni(blks[f].isize), at = (s - mk_uni(slice0s[f])) * MK_CRC_SLICE;
+  if (at >= isize) return; /* (cannot happen: the host counted the slices from the same sizes) */
+  const uint32_t n = isize - at < MK_CRC_SLICE ? isize - at : MK_CRC_SLICE;
+  const uint32_t r = mk_crc_wave(text + mk_uni(blks[f].out_off) + at, n, crctab, mat[wave], lane, false);
+  if (lane == 0u) slice_crc[s] = r;
+}
+
+/* a * b mod the CRC polynomial, bit-reflected (x^0 is bit 31); x^(8n), which advances a register over n zero bytes */
+__device__ __forceinline__ uint32_t mk_crc_mul(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+  for (uint32_t m = 1u << 31; m; m >>= 1) {
+    if (a & m) p ^= b;
+    b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
+  }
+  return p;
+}
+__device__ __forceinline__ uint32_t mk_crc_xpow8(uint32_t n) {
+  uint32_t p = 1u << 31, sq = 0x00800000u;
+  for (; n; n >>= 1) {
+    if (n & 1u) p = mk_crc_mul(sq, p);
+    sq = mk_crc_mul(sq, sq);
+  }
+  return p;
+}
+/* one THREAD per member: its slices' registers in order, each advanced over what follows it; the all-ones start value advanced over
+ * the whole text and the final complement; the comparison with the trailer goes into a status that was MK_INFL_OK */
+__global__ void __launch_bounds__(64) mk_crc32_combine_kernel(const mk_infl_blk *__restrict__ blks, const uint32_t *__restrict__ slice0s, uint32_t nfiles,
+                                                              const uint32_t *__restrict__ slice_crc, uint32_t *status, uint32_t *crc_out) {
+  const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+  if (f >= nfiles) return;
+  const uint32_t isize = blks[f].isize, s0 = slice0s[f], ns = slice0s[f + 1u] - s0;
+  const uint32_t xfull = mk_crc_xpow8(MK_CRC_SLICE);
+  uint32_t tot = 0;
+  for (uint32_t j = 0; j < ns; j++) {
+    const uint32_t len = j + 1u < ns ? MK_CRC_SLICE : isize - j * MK_CRC_SLICE;
+    tot = mk_crc_mul(len == MK_CRC_SLICE ? xfull : mk_crc_xpow8(len), tot) ^ slice_crc[s0 + j];
+  }
+  const uint32_t crc = ~(tot ^ mk_crc_mul(mk_crc_xpow8(isize), 0xffffffffu));
+  crc_out[f] = crc;
+  if (status[f] == MK_INFL_OK && crc != blks[f].crc) status[f] = MK_INFL_CRC;
 }
 
 /* ---- FASTQ framing of text in HBM ---------------------------------------------------------------------------------------------
@@ -678,7 +763,16 @@ extern "C" int mk_inflate_last_kernel_ms(mk_inflate *h, double *inflate_ms, doub
 /* ---- launches, on any stream ------------------------------------------------------------------------------------------------ */
 static hipError_t mk_launch_inflate(hipStream_t s, const uint8_t *d_comp, const mk_infl_blk *d_blks, uint32_t nblocks, uint8_t *d_text, uint32_t *d_status) {
   if (!nblocks) return hipSuccess;
-  hipLaunchKernelGGL(mk_inflate_kernel, dim3((nblocks + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, s, d_comp, d_blks, nblocks, d_text, d_status);
+  hipLaunchKernelGGL(mk_inflate_kernel<false>, dim3((nblocks + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, s, d_comp, d_blks, nblocks, d_text, d_status);
+  return hipGetLastError();
+}
+hipError_t mk_gz_launch(hipStream_t s, const uint8_t *d_comp, const void *d_tab, uint32_t n, uint32_t nslices, uint8_t *d_text, uint32_t *d_work) {
+  if (!n) return hipSuccess;
+  const mk_infl_blk *blks = (const mk_infl_blk *)d_tab;
+  const uint32_t *slice0s = (const uint32_t *)((const uint8_t *)d_tab + mk_gz_slice0_at(n));
+  hipLaunchKernelGGL(mk_inflate_kernel<true>, dim3((n + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, s, d_comp, blks, n, d_text, d_work);
+  if (nslices) hipLaunchKernelGGL(mk_crc32_files_kernel, dim3((nslices + 3u) / 4u), dim3(256), 0, s, (const uint8_t *)d_text, blks, slice0s, n, nslices, d_work + 4u * (size_t)n);
+  hipLaunchKernelGGL(mk_crc32_combine_kernel, dim3((n + 63u) / 64u), dim3(64), 0, s, blks, slice0s, n, (const uint32_t *)(d_work + 4u * (size_t)n), d_work, d_work + 3u * (size_t)n);
   return hipGetLastError();
 }
 static inline uint32_t mk_fq_ntiles(uint32_t e1) { return e1 ? (e1 + MK_FQ_TILE - 1) / MK_FQ_TILE : 1u; }
@@ -737,6 +831,56 @@ extern "C" int mk_inflate_blocks(mk_inflate *h, const uint8_t *comp, size_t comp
   MK_INFL_HIP(h, hipMemcpyAsync(h->h_status, h->d_status, nblocks * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
   memcpy(status, h->h_status, nblocks * sizeof(uint32_t));
+  if (out_host && text_end) MK_INFL_HIP(h, hipMemcpy(out_host, h->d_text, text_end, hipMemcpyDeviceToHost));
+  float ms = 0.f;
+  MK_INFL_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+  h->inflate_ms = ms;
+  return MK_OK;
+}
+
+extern "C" int mk_inflate_members(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_gz_member *members, uint32_t nmembers,
+                                  uint8_t *out_host, size_t out_cap, mk_gz_member_result *res) {
+  if (!h || (!comp && comp_bytes) || (!members && nmembers) || !res) return MK_ERR_ARG;
+  if (nmembers == 0) return MK_OK;
+  if (nmembers > (1u << 20) || comp_bytes >= (1ull << 31)) return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_members: at most 2^20 members and 2 GiB a call");
+  uint64_t text_end = 0, nslices = 0;
+  for (uint32_t i = 0; i < nmembers; i++) {
+    const mk_gz_member &m = members[i];
+    if (m.pay_off + (uint64_t)m.pay_len > comp_bytes || m.isize > MK_BATCH_FILE_MAX || m.out_off + m.isize > (1ull << 30))
+      return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_members: member %u lies outside the buffers", i);
+    if (m.out_off + m.isize > text_end) text_end = m.out_off + m.isize;
+    nslices += mk_gz_slices(m.isize);
+  }
+  if (out_host && out_cap < text_end) return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_members: out_cap too small");
+  MK_INFL_HIP(h, hipSetDevice(h->device));
+  const uint64_t tab_at = (comp_bytes + 15u) & ~(uint64_t)15u, stage_bytes = tab_at + mk_gz_table_bytes(nmembers);
+  const uint64_t words = mk_gz_work_words(nmembers, (uint32_t)nslices);
+  int rc = mk_infl_grow_pinned(h, &h->h_stage, &h->stage_cap, stage_bytes);
+  if (!rc) rc = mk_infl_grow(h, &h->d_comp, &h->comp_cap, stage_bytes + 64);
+  if (!rc) rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(text_end));
+  if (!rc) rc = mk_infl_grow(h, &h->d_status, &h->status_cap, words);
+  if (!rc) rc = mk_infl_grow_pinned(h, &h->h_status, &h->h_status_cap, 4u * (uint64_t)nmembers);
+  if (rc) return rc;
+  memcpy(h->h_stage, comp, comp_bytes);
+  memset(h->h_stage + comp_bytes, 0, tab_at - comp_bytes);
+  mk_infl_blk *tab = (mk_infl_blk *)(h->h_stage + tab_at);
+  uint32_t *slice0s = (uint32_t *)(h->h_stage + tab_at + mk_gz_slice0_at(nmembers));
+  uint32_t s0 = 0;
+  for (uint32_t i = 0; i < nmembers; i++) {
+    const mk_gz_member &m = members[i];
+    tab[i] = mk_infl_blk{(uint32_t)m.pay_off, m.pay_len, (uint32_t)m.out_off, m.isize, m.crc32};
+    slice0s[i] = s0;
+    s0 += mk_gz_slices(m.isize);
+  }
+  slice0s[nmembers] = s0;
+  MK_INFL_HIP(h, hipMemcpyAsync(h->d_comp, h->h_stage, stage_bytes, hipMemcpyHostToDevice, h->stream));
+  MK_INFL_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  MK_INFL_HIP(h, mk_gz_launch(h->stream, h->d_comp, h->d_comp + tab_at, nmembers, s0, h->d_text, h->d_status));
+  MK_INFL_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  MK_INFL_HIP(h, hipMemcpyAsync(h->h_status, h->d_status, 4u * (size_t)nmembers * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
+  for (uint32_t i = 0; i < nmembers; i++)
+    res[i] = mk_gz_member_result{h->h_status[i], h->h_status[nmembers + i], h->h_status[2u * (size_t)nmembers + i], h->h_status[3u * (size_t)nmembers + i]};
   if (out_host && text_end) MK_INFL_HIP(h, hipMemcpy(out_host, h->d_text, text_end, hipMemcpyDeviceToHost));
   float ms = 0.f;
   MK_INFL_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
