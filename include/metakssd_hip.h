@@ -685,6 +685,7 @@ int mk_byread_last_kernel_ms(mk_byread *b, double *emit_ms, double *reverse_ms);
  *   mk_inflate_blocks     device: one wavefront inflates one member (stored, fixed and dynamic blocks) and checks its CRC32
  *   mk_fastq_frame_device device: mk_fastq_frame's rule (four lines a record, the sequence line with its '\n' is the row) on text in HBM
  *   mk_sketch_push_bgzf   the three bound to an engine: compressed bytes cross PCIe, rows go to mk_sketch_push_reads_device
+ *   mk_fastq_frame_q_device, mk_sketch_push_bgzf_q   the same for the other FASTQ reader (dist without -A: -n, -Q)
  * There is no CPU path for the device parts: mk_inflate_create fails with MK_ERR_NO_DEVICE without a HIP device. */
 typedef struct mk_bgzf_block {
   uint64_t in_off;  /* where the member starts in the file */
@@ -732,7 +733,17 @@ int mk_inflate_blocks(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, con
  * or n when final; *longest = the longest line of any kind.  MK_ERR_FORMAT: a line of 4095 characters or more. */
 int mk_fastq_frame_device(mk_inflate *h, const uint8_t *text, size_t n, int final, uint8_t *rows_host, size_t rows_cap,
                           uint32_t *stride, uint64_t *nrows, size_t *consumed, uint32_t *longest);
-/* kernels of the last mk_inflate_blocks / mk_fastq_frame_device, in ms (HIP events on the handle's stream) */
+/* mk_fastq_frame_q on the device (fastq2co's reader, iseq2comem.c:343-379: its record rule and the -Q mask), one row a record:
+ * a record is a row iff all four of its lines end in '\n' (so *nrecords = *nrows = newlines / 4), except the first record of the
+ * file (final != 0, records_before == 0, no complete record in the text), which is a row whenever its sequence line exists; the
+ * row is the sequence line without its '\n', every base whose byte of the quality line (signed char; the line's own '\n' counts
+ * as its last byte, 0 behind it) is below qmin written as 'N' (qmin <= -128: none), then '\n' and zeros.  *stride, rows_host,
+ * *consumed, *longest as in mk_fastq_frame_device.  No TL: the device cuts no windows, a line of 4095 characters or more is
+ * MK_ERR_FORMAT although fastq2co reads lines of up to 19998 -- the caller frames such a text on the host. */
+int mk_fastq_frame_q_device(mk_inflate *h, const uint8_t *text, size_t n, int final, int32_t qmin, uint64_t records_before,
+                            uint8_t *rows_host, size_t rows_cap, uint32_t *stride, uint64_t *nrows, uint64_t *nrecords,
+                            size_t *consumed, uint32_t *longest);
+/* kernels of the last mk_inflate_blocks / mk_fastq_frame_device / mk_fastq_frame_q_device, in ms (HIP events on the handle's stream) */
 int mk_inflate_last_kernel_ms(mk_inflate *h, double *inflate_ms, double *frame_ms);
 
 typedef struct mk_bgzf_opts {
@@ -755,7 +766,13 @@ typedef struct mk_bgzf_stats {
  * pushed, the sketch must be abandoned) or a line of 4095+ characters (st->bad_block == -1).  Engines with MK_OPT_SPLIT_CUS:
  * MK_ERR_STATE.  Returns when the device is done with the file. */
 int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, uint64_t first_ordinal, mk_bgzf_stats *st);
-const char *mk_bgzf_last_error(void); /* text of the calling thread's last failed mk_sketch_push_bgzf */
+/* The same for a sketch begun with mk_sketch_begin_occ (dist without -A; replaces the `zcat -fc` pipe in front of fastq2co's reader,
+ * iseq2comem.c:343-379): rows and errors are those of mk_fastq_frame_q_device over the inflated text with final != 0 and
+ * records_before == 0; chunks, the two in flight, the carry, the statistics and MK_ERR_STATE as above.  A line of 4095+ characters
+ * (MK_ERR_FORMAT, st->bad_block == -1) may be reported after rows of earlier chunks have been pushed: such a file is inside
+ * fastq2co's contract, so the caller abandons the sketch and reads the file through the host framer (mk_fastq_frame_q). */
+int mk_sketch_push_bgzf_q(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int32_t qmin, uint64_t first_ordinal, mk_bgzf_stats *st);
+const char *mk_bgzf_last_error(void); /* text of the calling thread's last failed mk_sketch_push_bgzf / mk_sketch_push_bgzf_q */
 /* the stream the engine's kernels are queued on now and its device, for work that must be ordered with them (staged rows are
  * flushed first).  MK_ERR_STATE with MK_OPT_SPLIT_CUS (two queues: no single stream orders with the scan). */
 int mk_engine_get_stream(mk_engine *e, void **hip_stream, int *device);

@@ -252,8 +252,11 @@ def _load():
         "mk_inflate_destroy": [vp],
         "mk_inflate_blocks": [vp, vp, C.c_size_t, C.POINTER(BgzfBlockC), u64, vp, C.c_size_t, vp],
         "mk_fastq_frame_device": [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u64), C.POINTER(C.c_size_t), C.POINTER(u32)],
+        "mk_fastq_frame_q_device": [vp, vp, C.c_size_t, C.c_int, i32, u64, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u64), C.POINTER(u64),
+                                    C.POINTER(C.c_size_t), C.POINTER(u32)],
         "mk_inflate_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "mk_sketch_push_bgzf": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), u64, C.POINTER(BgzfStatsC)],
+        "mk_sketch_push_bgzf_q": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), i32, u64, C.POINTER(BgzfStatsC)],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)
@@ -532,13 +535,16 @@ class Engine:
         """FASTQ without -A (fastq2co): ids of keys seen at least min_occurrence times"""
         _check(lib.mk_sketch_begin_occ(self.h, min_occurrence), self.h)
 
-    def push_bgzf(self, path, chunk_bytes=0, first_ordinal=0):
+    def push_bgzf(self, path, chunk_bytes=0, first_ordinal=0, qmin=None):
         """a BGZF-compressed FASTQ file into the sketch in progress (mk_sketch_push_bgzf) -> BgzfStatsC; a damaged member or a
         long line raises MkError(MK_ERR_FORMAT) with the statistics in .stats"""
         o, st = BgzfOptsC(chunk_bytes, 0), BgzfStatsC()
         fd = os.open(path, os.O_RDONLY)
         try:
-            rc = lib.mk_sketch_push_bgzf(self.h, fd, os.fstat(fd).st_size, C.byref(o), first_ordinal, C.byref(st))
+            if qmin is None:
+                rc = lib.mk_sketch_push_bgzf(self.h, fd, os.fstat(fd).st_size, C.byref(o), first_ordinal, C.byref(st))
+            else:
+                rc = lib.mk_sketch_push_bgzf_q(self.h, fd, os.fstat(fd).st_size, C.byref(o), qmin, first_ordinal, C.byref(st))
         finally:
             os.close(fd)
         if rc:
@@ -546,6 +552,10 @@ class Engine:
             err.stats = st
             raise err
         return st
+
+    def push_bgzf_q(self, path, qmin=0, chunk_bytes=0, first_ordinal=0):
+        """the same for a sketch begun with begin_occ (mk_sketch_push_bgzf_q): fastq2co's record rule and its -Q mask"""
+        return self.push_bgzf(path, chunk_bytes, first_ordinal, qmin=qmin)
 
     def push_reads(self, rows, stride, first_read_ordinal=0):
         """rows: host numpy u8 array of nreads*stride bytes (stride | MK_ROWS_PACKED: 64-byte packed rows)"""
@@ -1271,6 +1281,16 @@ class Inflate:
         rc = lib.mk_fastq_frame_device(self.h, b.ctypes.data if len(b) else None, len(b), 1 if final else 0, rows.ctypes.data, cap,
                                        C.byref(stride), C.byref(nrows), C.byref(used), C.byref(longest))
         return rows[: nrows.value * stride.value], stride.value, nrows.value, used.value, longest.value, rc
+
+    def frame_q(self, text, qmin=0, final=True, records_before=0):
+        """mk_fastq_frame_q_device -> (rows u8 [nrows * stride], stride, nrows, nrecords, consumed, longest line, rc)"""
+        b = np.frombuffer(bytes(text), dtype=np.uint8)
+        cap = (len(b) // 4 + 1) * 4096 if len(b) < (1 << 16) else len(b) * 4 + 4096
+        rows = np.zeros(cap, dtype=np.uint8)
+        stride, nrows, nrec, used, longest = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_size_t(0), C.c_uint32(0)
+        rc = lib.mk_fastq_frame_q_device(self.h, b.ctypes.data if len(b) else None, len(b), 1 if final else 0, qmin, records_before,
+                                         rows.ctypes.data, cap, C.byref(stride), C.byref(nrows), C.byref(nrec), C.byref(used), C.byref(longest))
+        return rows[: nrows.value * stride.value], stride.value, nrows.value, nrec.value, used.value, longest.value, rc
 
     def kernel_ms(self):
         a, b = C.c_double(0.0), C.c_double(0.0)

@@ -150,10 +150,12 @@ static int g_mmap_input = 0;  /* --mmap-input: the FASTQ file is mapped and the 
 static int g_early_chunks = 96; /* --early-chunks: chunks of a FASTQ file framed before the engine is there (mk_fastq_opts::early_chunks) */
 static int g_frame_early = 0; /* --frame-early: every chunk of a FASTQ file may be framed at once, also while the runtime and the engine come up (measurement) */
 static int g_ahead = MK_DEFAULT_AHEAD; /* --ahead: row buffers the FASTQ stream's framers may run ahead of the pushes by */
-static int g_no_device_inflate = 0; /* --no-device-inflate: BGZF inputs through `zcat -fc` like every other .gz (measurement) */
+static int g_no_device_inflate = 0; /* --no-device-inflate: BGZF inputs through `zcat -fc` like every other .gz (measurement); undoes --device-inflate */
 static int g_gz_batches = 0;        /* --device-inflate: single-member .gz genomes of a directory travel in gz batches and are inflated on the device.
                                      * Off by default: one wavefront decodes 7 MB/s, a batch of 64 genomes of 4 MB takes 0.54 s, and sixteen zcat
                                      * children are 6-14 times faster on 1 024 genomes */
+static int g_device_inflate_q = 0;  /* --device-inflate: a BGZF-compressed FASTQ on the -n / -Q reader (dist without -A) is inflated, framed and quality-masked on
+                                     * the device (mk_sketch_push_bgzf_q), 11-12 times the zcat pipe on 2 M reads.  Opt-in: without the switch this input keeps zcat */
 static uint64_t g_inflate_chunk_bytes = 0; /* --inflate-chunk-kib: text bytes per chunk of the device route (test hook; 0 = the library's default) */
 static int g_timing = 0; /* --timing */
 static int g_component_sz = 8; /* --component-sz: the reference's compile-time COMPONENT_SZ (global_basic.h:35-37) */
@@ -207,7 +209,8 @@ typedef struct {
   uint8_t *arena; /* row-buffer pool of the FASTQ stream: an anonymous mapping, pinned piece by piece behind the framers (pin_*) */
   size_t arena_bytes;
   struct pinner *pin;
-  int bgzf_ok; /* one engine on one GPU: a BGZF-compressed FASTQ on the -A reader is inflated on the device (sketch_fastq_bgzf) */
+  int bgzf_ok; /* one engine on one GPU: a BGZF-compressed FASTQ is inflated on the device (sketch_fastq_bgzf): on the -A reader by default,
+                * on the -n / -Q reader with --device-inflate */
 } ctx_t;
 
 #define CHECK(e, call)                                                  \
@@ -630,9 +633,12 @@ static void report_route(const char *path, const char *route, const mk_bgzf_stat
 }
 
 /* a .gz that is a BGZF chain from its first byte to its last (mk_bgzf_scan) is inflated, checked and framed on the device; 0: not
- * such a file, the caller goes on with `zcat -fc`, with today's behaviour and messages */
+ * such a file, the caller goes on with `zcat -fc`, with today's behaviour and messages.  The -n / -Q reader (c->occ) takes this
+ * route only with --device-inflate, and a file with a line of 4095+ characters -- which fastq2co() reads (iseq2comem.c:319,343) and
+ * the device does not cut into windows -- comes back from it: what has been pushed is finished and dropped, the caller begins the
+ * sketch anew and reads the file from its start through `zcat -fc`; --timing says so ("fallback": "long line"). */
 static int sketch_fastq_bgzf(ctx_t *c, const char *path) {
-  if (!c->bgzf_ok || c->occ || g_no_device_inflate || !has_suffix(path, ".gz")) return 0;
+  if (!c->bgzf_ok || (c->occ && !g_device_inflate_q) || g_no_device_inflate || !has_suffix(path, ".gz")) return 0;
   const int fd = open(path, O_RDONLY);
   if (fd < 0) return 0;
   struct stat st;
@@ -648,13 +654,22 @@ static int sketch_fastq_bgzf(ctx_t *c, const char *path) {
   memset(&o, 0, sizeof o);
   o.chunk_bytes = g_inflate_chunk_bytes;
   mk_bgzf_stats bs;
-  const int rc = mk_sketch_push_bgzf(e, fd, (size_t)st.st_size, &o, c->next_ordinal, &bs);
+  const int rc = c->occ ? mk_sketch_push_bgzf_q(e, fd, (size_t)st.st_size, &o, c->qmin, c->next_ordinal, &bs)
+                        : mk_sketch_push_bgzf(e, fd, (size_t)st.st_size, &o, c->next_ordinal, &bs);
   close(fd);
   if (rc == MK_ERR_FORMAT && bs.bad_block >= 0)
     die("%s: BGZF block %lld is damaged (%s): the input was not read completely", path, (long long)bs.bad_block, mk_inflate_status_text(bs.bad_status));
+  if (rc == MK_ERR_FORMAT && c->occ) {
+    mk_result dropped;
+    const int frc = mk_sketch_finish(e, &dropped); /* rows of earlier chunks: finished and dropped, the next push begins anew */
+    if (frc != MK_OK && frc != MK_ERR_CROWDED) die("mk_sketch_finish failed (%d): %s", frc, mk_last_error(e));
+    c->begun = 0;
+    g_gz_fallback = "long line";
+    return 0;
+  }
   if (rc == MK_ERR_FORMAT)
     die("%s: FASTQ line longer than the reference's fgets() width (%s): outside the framing contract", path, "4094 characters, iseq2comem.c:656,673");
-  if (rc != MK_OK) die("mk_sketch_push_bgzf failed (%d): %s", rc, mk_bgzf_last_error());
+  if (rc != MK_OK) die("%s failed (%d): %s", c->occ ? "mk_sketch_push_bgzf_q" : "mk_sketch_push_bgzf", rc, mk_bgzf_last_error());
   c->next_ordinal += bs.rows;
   c->nrows_total += bs.rows;
   c->t_last_push = now_s() - g_t0;
@@ -666,6 +681,7 @@ static void sketch_fastq(ctx_t *c, const char *path) {
   if (sketch_fastq_mapped(c, path)) return;
   if (sketch_fastq_bgzf(c, path)) return;
   if (is_compressed(path)) report_route(path, "zcat", NULL);
+  g_gz_fallback = NULL;
   ensure_buffers(c);
   input_t in;
   if (!open_input(path, &in)) die("mtfastq2koc():%s: %s", path, strerror(errno));
@@ -2666,8 +2682,10 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "--quiet")) quiet = 1;
     else if (!strcmp(argv[i], "--component-sz") && i + 1 < argc) g_component_sz = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--timing")) timing = g_timing = 1;
-    else if (!strcmp(argv[i], "--no-device-inflate")) { g_no_device_inflate = 1; g_gz_batches = 0; }
-    else if (!strcmp(argv[i], "--device-inflate")) { g_no_device_inflate = 0; g_gz_batches = 1; }
+    else if (!strcmp(argv[i], "--no-device-inflate")) { g_no_device_inflate = 1; g_gz_batches = 0; g_device_inflate_q = 0; }
+    /* --device-inflate: the two opt-in device routes -- single-member .gz genomes in gz batches and a BGZF FASTQ on
+     * the -n / -Q reader (4.12); the -A reader's BGZF route needs no switch.  The later of the two switches holds. */
+    else if (!strcmp(argv[i], "--device-inflate")) { g_no_device_inflate = 0; g_gz_batches = 1; g_device_inflate_q = 1; }
     else if (!strcmp(argv[i], "--inflate-chunk-kib") && i + 1 < argc) g_inflate_chunk_bytes = (uint64_t)atoll(argv[++i]) << 10;
     else if (!strcmp(argv[i], "--chunk-mib") && i + 1 < argc) chunk_bytes = (uint64_t)atoi(argv[++i]) << 20;
     else if (!strcmp(argv[i], "--inflight") && i + 1 < argc) inflight = atoi(argv[++i]); /* row buffers queued for copying */

@@ -31,7 +31,14 @@
  * The framing rule is mk_fastq_frame_range's (host/mk_frontend.c) and depends on line numbers only: record r is lines 4r..4r+3, it
  * gives a row iff its fourth line has at least one byte, the row is line 4r+1 with its '\n'.  (One difference, outside the contract
  * either way: a line of 4095+ characters is refused wherever it stands, also in a last record that lacks lines.)
- * Bound of each kernel: DESIGN.md 4.10.
+ *   mk_fq_reduce_q_kernel / mk_fq_rows_q_kernel / mk_fq_first_q_kernel
+ *                        the same for fastq2co's reader (dist without -A: -n, -Q), whose rule is mk_fastq_frame_q_range's: record r
+ *                        gives a row iff all four of its lines end in '\n', the row is line 4r+1 with the bases whose byte of line
+ *                        4r+3 is below -Q written as 'N'.  The reduce walk also leaves where every record's quality line starts and
+ *                        how long it is (8 bytes a record); the rows kernel masks while it copies.  The first record of a file that
+ *                        holds no complete one is walked all the same (iseq2comem.c:343-349): one wave does that serially.  No
+ *                        windows: a line of 4095+ characters is refused, the caller takes the host framer for such a file.
+ * Bound of each kernel: DESIGN.md 4.10, 4.12.
  */
 #include <hip/hip_runtime.h>
 #include "mk_poison.hip.h"
@@ -502,6 +509,8 @@ __device__ __forceinline__ uint32_t mk_wave_max(uint32_t v) {
   return v;
 }
 
+__device__ __forceinline__ uint32_t mk_fq_stride_dev(uint32_t need) { return MK_ROW_PITCH(need); }
+
 __global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_count_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
                                                                        uint32_t *tile_cnt, uint32_t *tile_last) {
   const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * MK_FQ_WAVES + (threadIdx.x >> 6);
@@ -644,6 +653,118 @@ __global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_rows_kernel(const uint
   }
 }
 
+/* ---- the same for fastq2co's reader (mk_fastq_frame_q_range, one row a record) -------------------------------------------------
+ * The scan kernel is launched with final == 0, so res->nrec = newlines / 4: only a record whose four lines are all terminated is a
+ * row, final call or not.  This walk adds what the rows kernel needs: qinfo[2r] = where record r's quality line starts (behind
+ * newline 4r + 2), qinfo[2r + 1] = its length with its '\n' (newline 4r + 3 minus the one in front of it), for r < nrec; both
+ * newlines exist for such a record, so both words are written, and start + length <= e1.  final: what lies behind the last newline
+ * is a line too (the longest-line test sees it).  Stores: res, and qinfo below 2 * min(nrec, qcap). */
+__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_reduce_q_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
+                                                                          const uint32_t *tile_base, int final, mk_fq_res *res,
+                                                                          uint32_t *qinfo, uint32_t qcap) {
+  const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * MK_FQ_WAVES + (threadIdx.x >> 6);
+  if (tile >= ntiles) return;
+  const uint32_t nl = res->nl;
+  uint32_t nrec = res->nrec;
+  if (nrec > qcap) nrec = qcap; /* (cannot happen: qcap >= text / 4 >= newlines / 4) */
+  uint32_t maxline = 0, maxseq = 0;
+  mk_fq_walk(buf, t0, e1, tile, tile_base[tile], lane, [&](uint32_t j, int32_t q, uint32_t p) {
+    const uint32_t len = (uint32_t)((int32_t)p - q), r = j >> 2, w = j & 3u;
+    maxline = len > maxline ? len : maxline;
+    if (final && j + 1u == nl) { const uint32_t tail = e1 - (p + 1u); maxline = tail > maxline ? tail : maxline; }
+    if (r >= nrec) return;
+    if (w == 1u) maxseq = len > maxseq ? len : maxseq;
+    else if (w == 2u) qinfo[2u * r] = p + 1u;
+    else if (w == 3u) {
+      qinfo[2u * r + 1u] = len;
+      if (r + 1u == nrec) res->consumed = p + 1u - t0;
+    }
+  });
+  maxline = mk_wave_max(maxline);
+  maxseq = mk_wave_max(maxseq);
+  if (lane == 0u) {
+    if (maxline) atomicMax(&res->maxline, maxline);
+    if (maxseq) atomicMax(&res->maxseq, maxseq);
+  }
+}
+
+/* base i of a row: the sequence byte, or 'N' when its quality byte (signed, 0 behind the quality line's end) is below qmin */
+__device__ __forceinline__ uint32_t mk_fq_qbyte(const uint8_t *buf, uint32_t start, uint32_t L, uint32_t qs, uint32_t qn, int32_t qmin, uint32_t i) {
+  uint32_t c = buf[start + i];
+  if (i < L && qmin > -128) {
+    const int32_t qv = i < qn ? (int32_t)(int8_t)buf[qs + i] : 0;
+    if (qv < qmin) c = (uint32_t)'N';
+  }
+  return c;
+}
+
+/* rows [r0, r1) of the chunk, r1 <= nrec: row r is line 4r + 1 with its '\n' (always there), quality-masked, zero-padded.  Loads:
+ * the sequence line the walk found, and qinfo's [start, start + length) clamped to [t0, e1). */
+__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_rows_q_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
+                                                                        const uint32_t *tile_base, uint32_t r0, uint32_t r1, uint32_t stride,
+                                                                        const uint32_t *qinfo, int32_t qmin, uint8_t *rows) {
+  __shared__ uint32_t ev_start[MK_FQ_WAVES][MK_FQ_TILE / 4], ev_len[MK_FQ_WAVES][MK_FQ_TILE / 4], ev_row[MK_FQ_WAVES][MK_FQ_TILE / 4];
+  __shared__ uint32_t ev_n[MK_FQ_WAVES];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, tile = blockIdx.x * MK_FQ_WAVES + wave;
+  if (tile >= ntiles) return;
+  if (lane == 0u) ev_n[wave] = 0u;
+  mk_lds_fence();
+  mk_fq_walk(buf, t0, e1, tile, tile_base[tile], lane, [&](uint32_t j, int32_t q, uint32_t p) {
+    const uint32_t r = j >> 2;
+    if ((j & 3u) != 1u || r < r0 || r >= r1) return;
+    const uint32_t at = atomicAdd(&ev_n[wave], 1u);
+    ev_start[wave][at] = (uint32_t)(q + 1);
+    ev_len[wave][at] = (uint32_t)((int32_t)p - q);
+    ev_row[wave][at] = r - r0;
+  });
+  mk_lds_fence();
+  const uint32_t n = ev_n[wave];
+  for (uint32_t e = 0; e < n; e++) {
+    const uint32_t start = ev_start[wave][e], row = ev_row[wave][e];
+    uint32_t len = ev_len[wave][e];
+    if (len > stride) len = stride; /* (cannot happen: the stride comes from the longest of these lines) */
+    uint32_t qs = qinfo[2u * (r0 + row)], qn = qinfo[2u * (r0 + row) + 1u];
+    if (qs < t0 || qs > e1) { qs = t0; qn = 0u; } /* (cannot happen: the reduce walk wrote both from newlines of the text) */
+    if (qn > e1 - qs) qn = e1 - qs;
+    const uint32_t L = len - 1u; /* len >= 1: the line's '\n' */
+    uint32_t *dst = (uint32_t *)(rows + (uint64_t)row * stride);
+    for (uint32_t o = 4u * lane; o < stride; o += 256u) {
+      uint32_t w = 0;
+      for (uint32_t k = 0; k < 4u; k++) if (o + k < len) w |= mk_fq_qbyte(buf, start, L, qs, qn, qmin, o + k) << (8u * k);
+      dst[o >> 2] = w;
+    }
+  }
+}
+
+/* The first record of a file without a complete one (fewer than four newlines, so fewer than four lines of at most 4095 bytes: the
+ * caller has checked the longest line): one wave finds the first three newlines, 64 bytes a step.  The sequence is line 2 without
+ * its '\n', the quality line is line 4 if the text has one, as far as it goes.  The row goes to rows[0, MK_ROW_PITCH(L + 1)), which
+ * is at most 4096 bytes; res->maxseq = L + 1 and res->nrec = 1 tell the host; a text without a second line leaves both as they are. */
+__global__ void __launch_bounds__(64) mk_fq_first_q_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, int32_t qmin, mk_fq_res *res, uint8_t *rows) {
+  const uint32_t lane = threadIdx.x;
+  uint32_t nlp[3] = {e1, e1, e1}, found = 0;
+  for (uint32_t b = t0; b < e1 && found < 3u; b += 64u) {
+    uint64_t m = __ballot(b + lane < e1 && buf[b + lane] == (uint8_t)'\n');
+    while (m && found < 3u) { nlp[found++] = b + (uint32_t)__builtin_ctzll(m); m &= m - 1ull; }
+  }
+  if (nlp[0] + 1u >= e1) return; /* no second line: no record */
+  const uint32_t start = nlp[0] + 1u;
+  uint32_t L = nlp[1] - start;
+  if (L > MK_FQ_LINE_MAX - 1u) L = MK_FQ_LINE_MAX - 1u; /* (cannot happen, see above) */
+  const uint32_t qs = nlp[2] < e1 ? nlp[2] + 1u : e1, qn = e1 - qs;
+  const uint32_t stride = mk_fq_stride_dev(L + 1u);
+  uint32_t *dst = (uint32_t *)rows;
+  for (uint32_t o = 4u * lane; o < stride; o += 256u) {
+    uint32_t w = 0;
+    for (uint32_t k = 0; k < 4u; k++) {
+      if (o + k < L) w |= mk_fq_qbyte(buf, start, L, qs, qn, qmin, o + k) << (8u * k);
+      else if (o + k == L) w |= (uint32_t)'\n' << (8u * k);
+    }
+    dst[o >> 2] = w;
+  }
+  if (lane == 0u) { res->maxseq = L + 1u; res->nrec = 1u; }
+}
+
 /* src[from, from + n) -> dst[to, to + n): the bytes behind a chunk's last complete record, n <= MK_FQ_CARRY */
 __global__ void __launch_bounds__(256) mk_fq_carry_kernel(const uint8_t *src, uint32_t from, uint8_t *dst, uint32_t to, uint32_t n) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[to + i] = src[from + i];
@@ -665,6 +786,8 @@ struct mk_inflate {
   uint64_t stage_cap = 0, comp_cap = 0, text_cap = 0, rows_cap = 0;
   uint32_t *d_status = nullptr, *h_status = nullptr, *d_tile_cnt = nullptr, *d_tile_last = nullptr;
   uint64_t status_cap = 0, h_status_cap = 0, tiles_cap = 0, tiles_last_cap = 0;
+  uint32_t *d_qinfo = nullptr; /* mk_fastq_frame_q_device: start and length of every record's quality line */
+  uint64_t qinfo_cap = 0;
   mk_fq_res *d_res = nullptr, *h_res = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   double inflate_ms = 0.0, frame_ms = 0.0;
@@ -741,7 +864,7 @@ extern "C" int mk_inflate_destroy(mk_inflate *h) {
   if (!h) return MK_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void *dev[] = {h->d_comp, h->d_text, h->d_rows, h->d_status, h->d_tile_cnt, h->d_tile_last, h->d_res};
+  void *dev[] = {h->d_comp, h->d_text, h->d_rows, h->d_status, h->d_tile_cnt, h->d_tile_last, h->d_qinfo, h->d_res};
   for (void *p : dev) (void)hipFree(p);
   void *pin[] = {h->h_stage, h->h_status, h->h_res};
   for (void *p : pin) if (p) (void)hipHostFree(p);
@@ -795,6 +918,33 @@ static hipError_t mk_launch_frame_rows(hipStream_t s, const uint8_t *d_buf, uint
   return hipGetLastError();
 }
 static inline uint32_t mk_fq_stride(uint32_t maxseq) { const uint32_t need = maxseq ? maxseq : 1u; return MK_ROW_PITCH(need); }
+
+/* fastq2co's reader.  Records a text of n bytes can hold: four newlines each */
+static inline uint32_t mk_fq_qcap(uint64_t n) { return (uint32_t)(n / 4u + 1u); }
+static hipError_t mk_launch_frame_count_q(hipStream_t s, const uint8_t *d_buf, uint32_t t0, uint32_t e1, int final, uint32_t *d_tile_cnt, uint32_t *d_tile_last,
+                                          const uint32_t *d_status, uint32_t nblocks, mk_fq_res *d_res, uint32_t *d_qinfo, uint32_t qcap) {
+  const uint32_t nt = mk_fq_ntiles(e1), grid = (nt + MK_FQ_WAVES - 1) / MK_FQ_WAVES;
+  hipLaunchKernelGGL(mk_fq_count_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, d_tile_cnt, d_tile_last);
+  hipLaunchKernelGGL(mk_fq_scan_kernel, dim3(1), dim3(1024), 0, s, d_tile_cnt, (const uint32_t *)d_tile_last, nt, t0, e1, 0, d_status, nblocks, d_res);
+  hipLaunchKernelGGL(mk_fq_reduce_q_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, (const uint32_t *)d_tile_cnt, final, d_res, d_qinfo, qcap);
+  return hipGetLastError();
+}
+static hipError_t mk_launch_frame_rows_q(hipStream_t s, const uint8_t *d_buf, uint32_t t0, uint32_t e1, const uint32_t *d_tile_cnt, uint32_t r0, uint32_t r1,
+                                         uint32_t stride, const uint32_t *d_qinfo, int32_t qmin, uint8_t *d_rows) {
+  if (r1 <= r0) return hipSuccess;
+  const uint32_t nt = mk_fq_ntiles(e1), grid = (nt + MK_FQ_WAVES - 1) / MK_FQ_WAVES;
+  hipLaunchKernelGGL(mk_fq_rows_q_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, d_tile_cnt, r0, r1, stride, d_qinfo, qmin, d_rows);
+  return hipGetLastError();
+}
+/* what the read-back of mk_launch_frame_count_q means on the host: on a final call everything is consumed and a text without a
+ * newline is one line.  Returns whether mk_fq_first_q_kernel must look at the text: a final call, no record so far, none here, and
+ * a first line that ends (whether a second one follows it is the kernel's to see). */
+static inline bool mk_fq_res_q(mk_fq_res &r, uint32_t n, int final, uint64_t records_before) {
+  if (!final) return false;
+  r.consumed = n;
+  if (r.nl == 0u && n > r.maxline) r.maxline = n;
+  return records_before == 0 && r.nrec == 0u && r.nl > 0u;
+}
 
 /* ---- the two entry points with a copy-back (tests, tools) ---------------------------------------------------------------------- */
 extern "C" int mk_inflate_blocks(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_bgzf_block *blocks, uint64_t nblocks,
@@ -923,13 +1073,64 @@ extern "C" int mk_fastq_frame_device(mk_inflate *h, const uint8_t *text, size_t 
   return MK_OK;
 }
 
+extern "C" int mk_fastq_frame_q_device(mk_inflate *h, const uint8_t *text, size_t n, int final, int32_t qmin, uint64_t records_before,
+                                       uint8_t *rows_host, size_t rows_cap, uint32_t *stride, uint64_t *nrows, uint64_t *nrecords,
+                                       size_t *consumed, uint32_t *longest) {
+  if (!h || (!text && n) || !stride || !nrows || !nrecords || !consumed) return MK_ERR_ARG;
+  if (n >= (1ull << 30)) return mk_infl_fail(h, MK_ERR_ARG, "mk_fastq_frame_q_device: at most 2^30 bytes a call");
+  MK_INFL_HIP(h, hipSetDevice(h->device));
+  const uint32_t t0 = 0, e1 = (uint32_t)n, nt = mk_fq_ntiles(e1), qcap = mk_fq_qcap(n);
+  int rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(e1));
+  if (!rc) rc = mk_infl_grow(h, &h->d_tile_cnt, &h->tiles_cap, nt);
+  if (!rc) rc = mk_infl_grow(h, &h->d_tile_last, &h->tiles_last_cap, nt);
+  if (!rc) rc = mk_infl_grow(h, &h->d_qinfo, &h->qinfo_cap, 2u * (uint64_t)qcap);
+  if (!rc) rc = mk_infl_grow(h, &h->d_rows, &h->rows_cap, MK_FQ_LINE_MAX); /* (the first record's row, whatever its stride) */
+  if (rc) return rc;
+  if (n) MK_INFL_HIP(h, hipMemcpyAsync(h->d_text, text, n, hipMemcpyHostToDevice, h->stream));
+  MK_INFL_HIP(h, hipEventRecord(h->ev[2], h->stream));
+  MK_INFL_HIP(h, mk_launch_frame_count_q(h->stream, h->d_text, t0, e1, final != 0, h->d_tile_cnt, h->d_tile_last, nullptr, 0, h->d_res, h->d_qinfo, qcap));
+  MK_INFL_HIP(h, hipMemcpyAsync(h->h_res, h->d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, h->stream));
+  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
+  mk_fq_res r = *h->h_res;
+  const bool first = mk_fq_res_q(r, e1, final != 0, records_before);
+  if (longest) *longest = r.maxline;
+  *nrows = 0; *nrecords = 0; *consumed = 0; *stride = mk_fq_stride(r.maxseq);
+  if (r.maxline >= MK_FQ_LINE_MAX) return mk_infl_fail(h, MK_ERR_FORMAT, "a FASTQ line of 4095 characters or more");
+  if (first) {
+    hipLaunchKernelGGL(mk_fq_first_q_kernel, dim3(1), dim3(64), 0, h->stream, (const uint8_t *)h->d_text, t0, e1, qmin, h->d_res, h->d_rows);
+    MK_INFL_HIP(h, hipGetLastError());
+    MK_INFL_HIP(h, hipMemcpyAsync(h->h_res, h->d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, h->stream));
+    MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
+    r.nrec = h->h_res->nrec;
+    r.maxseq = h->h_res->maxseq;
+  }
+  const uint32_t sd = mk_fq_stride(r.maxseq);
+  *stride = sd;
+  if (rows_host && (uint64_t)r.nrec * sd > rows_cap) return mk_infl_fail(h, MK_ERR_ARG, "mk_fastq_frame_q_device: %u rows of %u bytes do not fit rows_cap", r.nrec, sd);
+  if (!first) {
+    rc = mk_infl_grow(h, &h->d_rows, &h->rows_cap, (uint64_t)r.nrec * sd);
+    if (rc) return rc;
+    MK_INFL_HIP(h, mk_launch_frame_rows_q(h->stream, h->d_text, t0, e1, h->d_tile_cnt, 0, r.nrec, sd, h->d_qinfo, qmin, h->d_rows));
+  }
+  MK_INFL_HIP(h, hipEventRecord(h->ev[3], h->stream));
+  if (rows_host && r.nrec) MK_INFL_HIP(h, hipMemcpyAsync(rows_host, h->d_rows, (uint64_t)r.nrec * sd, hipMemcpyDeviceToHost, h->stream));
+  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  MK_INFL_HIP(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+  h->frame_ms = ms;
+  *nrows = r.nrec;
+  *nrecords = r.nrec;
+  *consumed = r.consumed;
+  return MK_OK;
+}
+
 /* ---- the route bound to an engine -------------------------------------------------------------------------------------------- */
 namespace {
 struct mk_bgzf_run { /* everything mk_sketch_push_bgzf allocates, released on every way out */
   mk_bgzf_block *blocks = nullptr;
   hipStream_t copy = nullptr;
   uint8_t *h_stage[2] = {nullptr, nullptr}, *d_comp[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr}, *d_rows = nullptr;
-  uint32_t *d_status[2] = {nullptr, nullptr}, *d_tile_cnt = nullptr, *d_tile_last = nullptr;
+  uint32_t *d_status[2] = {nullptr, nullptr}, *d_tile_cnt = nullptr, *d_tile_last = nullptr, *d_qinfo = nullptr;
   mk_fq_res *d_res = nullptr, *h_res = nullptr;
   hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_res = nullptr, ev_i[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, ev_f[4] = {nullptr, nullptr, nullptr, nullptr};
   ~mk_bgzf_run() {
@@ -940,7 +1141,7 @@ struct mk_bgzf_run { /* everything mk_sketch_push_bgzf allocates, released on ev
       if (ev_up[s]) (void)hipEventDestroy(ev_up[s]);
       for (int k = 0; k < 2; k++) if (ev_i[s][k]) (void)hipEventDestroy(ev_i[s][k]);
     }
-    (void)hipFree(d_rows); (void)hipFree(d_tile_cnt); (void)hipFree(d_tile_last); (void)hipFree(d_res);
+    (void)hipFree(d_rows); (void)hipFree(d_tile_cnt); (void)hipFree(d_tile_last); (void)hipFree(d_qinfo); (void)hipFree(d_res);
     if (h_res) (void)hipHostFree(h_res);
     if (ev_res) (void)hipEventDestroy(ev_res);
     for (hipEvent_t e : ev_f) if (e) (void)hipEventDestroy(e);
@@ -957,7 +1158,8 @@ static thread_local char mk_bgzf_err[256];
     if (_r != hipSuccess) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s: %s", #call, hipGetErrorString(_r)); (void)hipStreamSynchronize(S); if (R.copy) (void)hipStreamSynchronize(R.copy); return MK_ERR_HIP; } \
   } while (0)
 
-extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, uint64_t first_ordinal, mk_bgzf_stats *st) {
+/* both readers' route: occ == false is mk_fastq_frame's rule (-A), occ == true mk_fastq_frame_q's (quality mask qmin) */
+static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, bool occ, int32_t qmin, uint64_t first_ordinal, mk_bgzf_stats *st) {
   if (!e || fd < 0) return MK_ERR_ARG;
   mk_bgzf_stats stats;
   memset(&stats, 0, sizeof stats);
@@ -1011,6 +1213,8 @@ extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_b
   MK_BGZF_HIP(mk_dev_alloc(&R.d_rows, rows_cap));
   MK_BGZF_HIP(mk_dev_alloc(&R.d_tile_cnt, (uint64_t)max_tiles * sizeof(uint32_t)));
   MK_BGZF_HIP(mk_dev_alloc(&R.d_tile_last, (uint64_t)max_tiles * sizeof(uint32_t)));
+  const uint32_t qcap = mk_fq_qcap(MK_FQ_CARRY + max_text);
+  if (occ) MK_BGZF_HIP(mk_dev_alloc(&R.d_qinfo, 2u * (uint64_t)qcap * sizeof(uint32_t)));
   MK_BGZF_HIP(mk_dev_alloc(&R.d_res, sizeof(mk_fq_res)));
   MK_BGZF_HIP(mk_pin_alloc(&R.h_res, sizeof(mk_fq_res), hipHostMallocDefault));
   MK_BGZF_HIP(hipEventCreateWithFlags(&R.ev_res, hipEventDisableTiming));
@@ -1054,7 +1258,8 @@ extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_b
     const int s = (int)(k & 1u), final = k + 1 == chunks.size();
     const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + (uint32_t)c.text, n = e1 - t0;
     MK_BGZF_HIP(hipEventRecord(R.ev_f[0], S));
-    MK_BGZF_HIP(mk_launch_frame_count(S, R.d_text[s], t0, e1, final, R.d_tile_cnt, R.d_tile_last, R.d_status[s], (uint32_t)(c.b1 - c.b0), R.d_res));
+    if (occ) MK_BGZF_HIP(mk_launch_frame_count_q(S, R.d_text[s], t0, e1, final, R.d_tile_cnt, R.d_tile_last, R.d_status[s], (uint32_t)(c.b1 - c.b0), R.d_res, R.d_qinfo, qcap));
+    else MK_BGZF_HIP(mk_launch_frame_count(S, R.d_text[s], t0, e1, final, R.d_tile_cnt, R.d_tile_last, R.d_status[s], (uint32_t)(c.b1 - c.b0), R.d_res));
     MK_BGZF_HIP(hipEventRecord(R.ev_f[1], S));
     MK_BGZF_HIP(hipMemcpyAsync(R.h_res, R.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
     MK_BGZF_HIP(hipEventRecord(R.ev_res, S));
@@ -1063,7 +1268,8 @@ extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_b
       if (rc) return rc;
     }
     MK_BGZF_HIP(hipEventSynchronize(R.ev_res)); /* the one wait per chunk: rows, longest line, consumed, status */
-    const mk_fq_res r = *R.h_res;
+    mk_fq_res r = *R.h_res;
+    const bool first = occ && mk_fq_res_q(r, n, final, stats.rows);
     float ms = 0.f;
     MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_i[s][0], R.ev_i[s][1]));
     stats.inflate_ms += ms;
@@ -1082,12 +1288,25 @@ extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_b
       result = MK_ERR_FORMAT;
       break;
     }
+    if (first) { /* no complete record in the whole file: its first one is walked all the same, if it has a sequence line */
+      hipLaunchKernelGGL(mk_fq_first_q_kernel, dim3(1), dim3(64), 0, S, (const uint8_t *)R.d_text[s], t0, e1, qmin, R.d_res, R.d_rows);
+      MK_BGZF_HIP(hipGetLastError());
+      MK_BGZF_HIP(hipMemcpyAsync(R.h_res, R.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
+      MK_BGZF_HIP(hipStreamSynchronize(S));
+      if (R.h_res->nrec) {
+        rc = mk_sketch_push_reads_device(e, R.d_rows, mk_fq_stride(R.h_res->maxseq), 1, ordinal);
+        if (rc) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
+        ordinal++;
+        stats.rows++;
+      }
+    }
     const uint32_t stride = mk_fq_stride(r.maxseq);
     const uint32_t per = (uint32_t)(rows_cap / stride);
     if (r.nrec) { MK_BGZF_HIP(hipEventRecord(R.ev_f[2], S)); }
     for (uint32_t r0 = 0; r0 < r.nrec; r0 += per) {
       const uint32_t r1 = r.nrec - r0 < per ? r.nrec : r0 + per;
-      MK_BGZF_HIP(mk_launch_frame_rows(S, R.d_text[s], t0, e1, R.d_tile_cnt, r0, r1, stride, R.d_rows));
+      if (occ) MK_BGZF_HIP(mk_launch_frame_rows_q(S, R.d_text[s], t0, e1, R.d_tile_cnt, r0, r1, stride, R.d_qinfo, qmin, R.d_rows));
+      else MK_BGZF_HIP(mk_launch_frame_rows(S, R.d_text[s], t0, e1, R.d_tile_cnt, r0, r1, stride, R.d_rows));
       if (r0 == 0) { MK_BGZF_HIP(hipEventRecord(R.ev_f[3], S)); rows_timed = true; }
       rc = mk_sketch_push_reads_device(e, R.d_rows, stride, r1 - r0, ordinal);
       if (rc) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
@@ -1107,6 +1326,14 @@ extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_b
   stats.t_total_s = mk_now_s() - t_begin;
   if (st) *st = stats;
   return result;
+}
+
+extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, uint64_t first_ordinal, mk_bgzf_stats *st) {
+  return mk_push_bgzf(e, fd, size, o, false, 0, first_ordinal, st);
+}
+
+extern "C" int mk_sketch_push_bgzf_q(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int32_t qmin, uint64_t first_ordinal, mk_bgzf_stats *st) {
+  return mk_push_bgzf(e, fd, size, o, true, qmin, first_ordinal, st);
 }
 
 extern "C" const char *mk_bgzf_last_error(void) { return mk_bgzf_err; }

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """tools/bench_bgzf.py -- BGZF-compressed FASTQ through `metakssd dist -L L3K11.shuf -A`: the device route (inflate, CRC32 and
 FASTQ framing on the GPU) against `--no-device-inflate` (the `zcat -fc` pipe, what every other .gz takes) and against `zcat -fc`
-alone; prints one JSON line.
+alone; prints one JSON line.  `--reader nQ`: the same legs on the other FASTQ reader (`-n 2 -Q 53` in place of `-A`), whose device route
+is opt-in: the device leg passes `--device-inflate`, and `--no-device-inflate` is what the command does without a switch.
 
 The input is bench.py's read stream (mk_synth_fastq_write_mt, same seed and read length), compressed to BGZF here with Python's
 zlib at level 1 and at level 6 (members of 65280 bytes of text, one raw deflate stream each, the end marker last).  Per level the
@@ -50,10 +51,14 @@ def write_bgzf(src, dst, level, procs):
     return os.path.getsize(dst)
 
 
+READERS = {"A": (["-A"], []), "nQ": (["-n", "2", "-Q", "53"], ["--device-inflate"])}  # reader -> (its flags, the device leg's switch)
+READER = READERS["A"]
+
+
 def run_cli(shuf, out, inp, extra):
     shutil.rmtree(out, ignore_errors=True)
     t0 = time.perf_counter()
-    r = subprocess.run([CLI, "dist", "-L", shuf, "-A", "-o", out, "--quiet", "--timing"] + extra + [inp], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=3000)
+    r = subprocess.run([CLI, "dist", "-L", shuf] + READER[0] + ["-o", out, "--quiet", "--timing"] + extra + [inp], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=3000)
     dt = time.perf_counter() - t0
     if r.returncode != 0:
         raise RuntimeError(r.stderr.decode(errors="replace")[-500:])
@@ -68,15 +73,18 @@ def main():
     ap.add_argument("--levels", default="1,6")
     ap.add_argument("--procs", type=int, default=16, help="processes that compress the fixture")
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--reader", default="A", choices=sorted(READERS), help="A: `dist -A` (mt_shortreads2koc's reader); nQ: `dist -n 2 -Q 53` (fastq2co's)")
     ap.add_argument("--rocprof", default=None, help="directory: one more device-route run per level under `rocprofv3 --kernel-trace --stats`")
     a = ap.parse_args()
+    global READER
+    READER = READERS[a.reader]
     from golden_cases import make_shuf
     from metakssd_amd import capi
     if capi.device_count() < 1:
         sys.exit("bench_bgzf: no HIP device")
     tmp = tempfile.mkdtemp(prefix="mkbgzf_", dir=a.workdir or ("/dev/shm" if os.path.isdir("/dev/shm") else None))
-    out = {"what": "`metakssd dist -L L3K11.shuf -A` on %d reads of %d bases as BGZF (members of %d text bytes), median of %d runs, legs taking turns"
-                   % (a.reads, READ_LEN, PAYLOAD, a.runs), "reads": a.reads, "levels": {}}
+    out = {"what": "`metakssd dist -L L3K11.shuf %s` on %d reads of %d bases as BGZF (members of %d text bytes), median of %d runs, legs taking turns"
+                   % (" ".join(READER[0]), a.reads, READ_LEN, PAYLOAD, a.runs), "reads": a.reads, "device_leg_switch": READER[1], "levels": {}}
     try:
         shuf = os.path.join(tmp, "L3K11.shuf")
         make_shuf("L3K11", shuf)
@@ -93,8 +101,8 @@ def main():
             dev, zc, zo, kin, kout, infl_ms, frame_ms = [], [], [], [], [], [], []
             d_dev, d_zc = os.path.join(tmp, "dev"), os.path.join(tmp, "zc")
             for _ in range(a.runs):
-                dt, route = run_cli(shuf, d_dev, gz, [])
-                assert route and route["route"] == "device-inflate", route
+                dt, route = run_cli(shuf, d_dev, gz, READER[1])
+                assert route and route["route"] == "device-inflate" and "fallback" not in route, route
                 dev.append(dt)
                 infl_ms.append(route["inflate_ms"]); frame_ms.append(route["frame_ms"])
                 kin.append(route["comp_bytes"] / route["inflate_ms"] / 1e6)
@@ -107,8 +115,8 @@ def main():
                 zo.append(time.perf_counter() - t0)
             if a.rocprof:
                 os.makedirs(a.rocprof, exist_ok=True)
-                subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", a.rocprof, "-o", "bgzf_l%d" % level, "--", CLI, "dist", "-L", shuf, "-A", "-o",
-                                os.path.join(tmp, "prof"), "--quiet", "--slow-exit", gz], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+                subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", a.rocprof, "-o", "bgzf%s_l%d" % ("" if a.reader == "A" else "_" + a.reader, level), "--", CLI, "dist", "-L", shuf] + READER[0] + ["-o",
+                                os.path.join(tmp, "prof"), "--quiet", "--slow-exit"] + READER[1] + [gz], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
             files = sorted(os.listdir(d_dev))
             equal = files == sorted(os.listdir(d_zc)) and all(filecmp.cmp(os.path.join(d_dev, f), os.path.join(d_zc, f), shallow=False) for f in files)
             md, mz, mo = statistics.median(dev), statistics.median(zc), statistics.median(zo)
