@@ -637,6 +637,44 @@ int mk_abv_search(mk_abv *a, int metric, uint32_t nq, const mk_binvec *q, const 
 /* measurement: device time of the last index's and the last search's kernels, from HIP events on the handle's stream */
 int mk_abv_last_kernel_ms(mk_abv *a, double *index_ms, double *search_ms);
 
+/* ---- `composite -r <ref> -q <qry>` with the marker database resident on the device -----------------------
+ * get_species_abundance() (command_composite.c:446-640) walks the whole reference for every query sample.  mk_composite inverts the
+ * reference once (k-mer id -> the reference sketches that hold it; duplicates kept), keeps it in HBM, and looks up only the samples'
+ * own ids.  A row is what the reference computes per (sample, reference sketch) with at least 6 shared k-mers (:599-613), v = the
+ * sample's counts of the shared k-mers, ascending, 1-based: kmer_num, sum (32-bit two's complement), median = v[kmer_num / 2],
+ * top = v[kmer_num], lastsum / lastn over n = (int)(kmer_num * 0.98) .. n <= kmer_num * 0.99.  The float divisions stay with the caller.
+ *   mk_composite_load_begin / _load_component   the database, once: one call per component (combco.c / combco.index.c with ref_num + 1
+ *                                               entries).  MK_ERR_ARG for a component of 2^32 or more ids.
+ *   mk_composite_query_begin / _query_component / _query_finish   a batch of samples: one call per component with the samples' slice of
+ *                                               combco.c / combco.c.a and its nsamples + 1 positions (index[0] = 0).  An id that occurs
+ *                                               more than once in one sample's slice counts at its first occurrence only (the
+ *                                               reference's dictionary finds that one).  finish gives the rows of sample k as
+ *                                               rows[row_end[k-1] .. row_end[k]) in print order: kmer_num descending, reference number
+ *                                               ascending among equals.  MK_ERR_STATE before the whole database is loaded.
+ * A batch whose hits exceed the hit buffer (MK_COMPOSITE_OPT_MAX_HITS, 2^26 by default), or whose samples * ref_num does not fit 32
+ * bits, is worked through in sub-ranges of whole samples; the result does not depend on the cuts.  One sample above the capacity
+ * grows the buffer (an error naming the sample if that fails).  Result pointers are library-owned, valid until the next call on the
+ * handle.  No CPU path: mk_composite_create fails with MK_ERR_NO_DEVICE without a HIP device. */
+typedef struct mk_composite mk_composite;
+typedef struct mk_composite_row {
+  uint32_t ref; /* reference sketch number */
+  int32_t kmer_num, sum, lastsum, lastn, median, top;
+} mk_composite_row;
+int mk_composite_create(int device, mk_composite **out);
+int mk_composite_destroy(mk_composite *h);
+const char *mk_composite_last_error(const mk_composite *h); /* h may be NULL: last error of a failed create */
+int mk_composite_load_begin(mk_composite *h, uint32_t ref_num, uint32_t comp_num);
+int mk_composite_load_component(mk_composite *h, uint32_t c, const uint32_t *ref_ids, const uint64_t *ref_index);
+int mk_composite_query_begin(mk_composite *h, uint32_t nsamples);
+int mk_composite_query_component(mk_composite *h, uint32_t c, const uint32_t *ids, const uint16_t *counts, const uint64_t *index);
+int mk_composite_query_finish(mk_composite *h, const mk_composite_row **rows, uint64_t *row_end /* [nsamples] */);
+enum { MK_COMPOSITE_OPT_MAX_HITS = 1 }; /* hit-buffer capacity in hits (tests: forces the splitting at small sizes) */
+int mk_composite_set_option(mk_composite *h, int option, int64_t value);
+/* measurement: device time of the load kernels since load_begin and of the query kernels since query_begin (HIP events on the handle's
+ * stream); hits and sub-ranges of the last finish */
+int mk_composite_last_kernel_ms(mk_composite *h, double *load_ms, double *query_ms);
+int mk_composite_last_counts(mk_composite *h, uint64_t *hits, uint64_t *ranges);
+
 /* ---- `dist --byread` and `reverse`: per-record id streams and k-mer recovery ---------------------------------------------
  * reads2mco() (iseq2comem.c:88-214) appends, for every accepted window of the file in text order, the id drtuple >> comp_code_bits
  * to combco.<drtuple % component_num> -- repeats and key 0 kept, no hashlimit -- and writes per component the cumulative id

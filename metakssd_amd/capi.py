@@ -233,6 +233,16 @@ def _load():
         "mk_abv_load": [vp, vp, u64, vp, u32, vp, u32],
         "mk_abv_search": [vp, C.c_int, u32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)],
         "mk_abv_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+        "mk_composite_create": [C.c_int, C.POINTER(vp)],
+        "mk_composite_destroy": [vp],
+        "mk_composite_load_begin": [vp, u32, u32],
+        "mk_composite_load_component": [vp, u32, vp, vp],
+        "mk_composite_query_begin": [vp, u32],
+        "mk_composite_query_component": [vp, u32, vp, vp, vp],
+        "mk_composite_query_finish": [vp, C.POINTER(vp), vp],
+        "mk_composite_set_option": [vp, C.c_int, C.c_int64],
+        "mk_composite_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+        "mk_composite_last_counts": [vp, C.POINTER(u64), C.POINTER(u64)],
         "mk_byread_create": [C.c_int, C.POINTER(vp)],
         "mk_byread_destroy": [vp],
         "mk_byread_begin": [vp, C.POINTER(ParamsC)],
@@ -270,6 +280,8 @@ def _load():
     lib.mk_mco_last_error.restype = C.c_char_p
     lib.mk_abv_last_error.argtypes = [vp]
     lib.mk_abv_last_error.restype = C.c_char_p
+    lib.mk_composite_last_error.argtypes = [vp]
+    lib.mk_composite_last_error.restype = C.c_char_p
     lib.mk_byread_last_error.argtypes = [vp]
     lib.mk_byread_last_error.restype = C.c_char_p
     lib.mk_inflate_last_error.argtypes = [vp]
@@ -1188,6 +1200,83 @@ MK_INFL_OK, MK_INFL_BAD_BLOCK, MK_INFL_BAD_LENGTHS, MK_INFL_BAD_CODE, MK_INFL_BA
 MK_INFL_TRAILING = 8
 MK_CRC_SLICE = 16384
 BGZF_FIELDS = ("in_off", "out_off", "in_len", "pay_off", "pay_len", "crc32", "isize")
+
+
+# mk_composite_row: what get_species_abundance() computes per (sample, reference sketch) (command_composite.c:599-613)
+COMPOSITE_ROW = np.dtype([("ref", "<u4"), ("kmer_num", "<i4"), ("sum", "<i4"), ("lastsum", "<i4"), ("lastn", "<i4"), ("median", "<i4"),
+                          ("top", "<i4")])
+MK_COMPOSITE_OPT_MAX_HITS = 1
+
+
+class Composite:
+    """`composite -r <markerdb> -q <sketch_dir>` with the marker database resident on the device (mk_composite_*)"""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        rc = lib.mk_composite_create(device, C.byref(self.h))
+        if rc:
+            raise MkError(rc, (lib.mk_composite_last_error(None) or b"").decode())
+
+    def _check(self, rc):
+        if rc:
+            raise MkError(rc, (lib.mk_composite_last_error(self.h) or b"").decode())
+
+    def set_option(self, option, value):
+        self._check(lib.mk_composite_set_option(self.h, option, value))
+
+    def load(self, ref_num, components):
+        """components: per component (ids uint32, index uint64[ref_num + 1]) = combco.c / combco.index.c of the database"""
+        self._check(lib.mk_composite_load_begin(self.h, ref_num, len(components)))
+        for c, (ids, index) in enumerate(components):
+            ids = np.ascontiguousarray(ids, dtype=np.uint32)
+            index = np.ascontiguousarray(index, dtype=np.uint64)
+            assert index.size == ref_num + 1
+            self._check(lib.mk_composite_load_component(self.h, c, ids.ctypes.data if ids.size else None, index.ctypes.data))
+
+    def query_begin(self, nsamples):
+        self._check(lib.mk_composite_query_begin(self.h, nsamples))
+
+    def query_component(self, c, ids, counts, index):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint16)
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+        self._check(lib.mk_composite_query_component(self.h, c, ids.ctypes.data if ids.size else None,
+                                                     counts.ctypes.data if counts.size else None, index.ctypes.data))
+
+    def query_finish(self, nsamples):
+        """-> per sample a COMPOSITE_ROW array in print order"""
+        out = C.c_void_p()
+        ends = np.zeros(max(nsamples, 1), np.uint64)
+        self._check(lib.mk_composite_query_finish(self.h, C.byref(out), ends.ctypes.data))
+        total = int(ends[nsamples - 1]) if nsamples else 0
+        if total:
+            buf = (C.c_char * (total * COMPOSITE_ROW.itemsize)).from_address(out.value)
+            rows = np.frombuffer(buf, dtype=COMPOSITE_ROW).copy()
+        else:
+            rows = np.zeros(0, COMPOSITE_ROW)
+        return [rows[(int(ends[k - 1]) if k else 0):int(ends[k])] for k in range(nsamples)]
+
+    def query(self, nsamples, components):
+        """components: per component (ids, counts, index uint64[nsamples + 1]) of the batch -> query_finish()'s rows"""
+        self.query_begin(nsamples)
+        for c, (ids, counts, index) in enumerate(components):
+            self.query_component(c, ids, counts, index)
+        return self.query_finish(nsamples)
+
+    def last_kernel_ms(self):
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self._check(lib.mk_composite_last_kernel_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def last_counts(self):
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(lib.mk_composite_last_counts(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def close(self):
+        if self.h:
+            lib.mk_composite_destroy(self.h)
+            self.h = C.c_void_p()
 
 
 def bgzf_scan(data=None, path=None):

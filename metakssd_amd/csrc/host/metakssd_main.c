@@ -1638,9 +1638,152 @@ static int composite_search(const char *refdir, int metric, int nargs, char **ar
   return 0;
 }
 
+/* one sample's rows, in print order, as the report line (command_composite.c:624) or as its .abv (:587-595, :615-636); the two float
+ * divisions and the running float sum are the reference's, on the host */
+typedef struct { int ref_idx; float pct; } composite_vec;
+static void composite_write_sample(const mk_composite_row *rows, uint64_t nrows, const char *qname, const char *refname, const char *refdir,
+                                   const char *outdir, int binvec, composite_vec *vec) {
+  char path[PATHLEN * 3 + 64];
+  FILE *vf = NULL;
+  if (binvec) { /* :573-581 */
+    char dir[PATHLEN * 2 + 32], qn[PATHLEN + 1];
+    if (strlen(outdir) < 3) snprintf(dir, sizeof dir, "%s/abundance_Vec", refdir);
+    else snprintf(dir, sizeof dir, "%s", outdir);
+    mkdir(dir, 0777);
+    snprintf(qn, sizeof qn, "%.*s", PATHLEN, qname);
+    const char *base = strrchr(qn, '/');
+    snprintf(path, sizeof path, "%s/%s.abv", dir, base ? base + 1 : qn);
+    if (!(vf = fopen(path, "wb"))) die("get_species_abundance():%s", path);
+  }
+  int num_pass = 0;
+  float vecsum = 0;
+  for (uint64_t i = 0; i < nrows; i++) {
+    const mk_composite_row *r = rows + i;
+    if (binvec) {
+      if (r->median > 1 && r->kmer_num > 7) {
+        vec[num_pass].ref_idx = (int)r->ref;
+        vec[num_pass].pct = (float)r->lastsum / r->lastn;
+        vecsum += vec[num_pass].pct;
+        num_pass++;
+      }
+    } else {
+      printf("%.*s\t%.*s\t%d\t%f\t%f\t%d\t%d\n", PATHLEN, qname, PATHLEN, refname + (size_t)PATHLEN * r->ref, r->kmer_num,
+             (float)r->sum / r->kmer_num, (float)r->lastsum / r->lastn, r->median, r->top);
+    }
+  }
+  if (vf) {
+    for (int i = 0; i < num_pass; i++) vec[i].pct = (vec[i].pct - 1) * 100 / (vecsum - num_pass);
+    fwrite(vec, 8, (size_t)num_pass, vf);
+    fclose(vf);
+  }
+}
+
+/* bytes [off, off + len) of a file; die() with the reference's text when it cannot be had */
+static void composite_read_range(const char *path, uint64_t off, void *dst, size_t len) {
+  FILE *f = fopen(path, "rb");
+  if (!f) die("get_species_abundance():%s", path);
+  if (len && (fseeko(f, (off_t)off, SEEK_SET) != 0 || fread(dst, 1, len, f) != len)) die("get_species_abundance():%s is shorter than its index says", path);
+  fclose(f);
+}
+
+/* `composite -r -q` with the marker database resident on the device (mk_composite): the database's components are read
+ * and loaded once; the samples go through in batches of at most batch_bytes of query ids, of whose files only the batch's byte ranges
+ * are read */
+static void composite_resident(const char *refdir, const char *qrydir, const char *outdir, int binvec, int device, int ref_n, int qry_n,
+                               int comp_num, const char *refname, const char *qryname, uint64_t batch_bytes, uint64_t *batches_out,
+                               uint64_t *hits_out, double *load_ms, double *query_ms) {
+  char path[PATHLEN * 3 + 64];
+  mk_composite *h;
+  if (mk_composite_create(device, &h) != MK_OK) die("mk_composite_create failed: %s", mk_composite_last_error(NULL));
+  if (mk_composite_load_begin(h, (uint32_t)ref_n, (uint32_t)comp_num) != MK_OK) die("get_species_abundance(): %s", mk_composite_last_error(h));
+  for (int c = 0; c < comp_num; c++) {
+    size_t n1, n2;
+    snprintf(path, sizeof path, "%s/combco.%d", refdir, c);
+    uint8_t *rco = read_whole(path, &n1);
+    if (!rco) die("get_species_abundance():%s", path);
+    snprintf(path, sizeof path, "%s/combco.index.%d", refdir, c);
+    uint8_t *ridx = read_whole(path, &n2);
+    if (!ridx || n2 < 8 * ((size_t)ref_n + 1)) die("get_species_abundance():%s", path);
+    if (((const uint64_t *)ridx)[ref_n] * 4 > n1) die("get_species_abundance(): component %d is shorter than its index says", c);
+    if (mk_composite_load_component(h, (uint32_t)c, (const uint32_t *)rco, (const uint64_t *)ridx) != MK_OK)
+      die("get_species_abundance(): %s", mk_composite_last_error(h));
+    free(rco); free(ridx);
+  }
+  /* the query's positions, every component */
+  uint64_t **qpos = malloc(sizeof(uint64_t *) * (size_t)(comp_num > 0 ? comp_num : 1));
+  for (int c = 0; c < comp_num; c++) {
+    size_t n4;
+    struct stat st;
+    snprintf(path, sizeof path, "%s/combco.index.%d", qrydir, c);
+    qpos[c] = (uint64_t *)read_whole(path, &n4);
+    if (!qpos[c] || n4 < 8 * ((size_t)qry_n + 1)) die("get_species_abundance():%s", path);
+    snprintf(path, sizeof path, "%s/combco.%d", qrydir, c);
+    if (stat(path, &st) != 0) die("get_species_abundance():%s", path);
+    const uint64_t nid = (uint64_t)st.st_size;
+    snprintf(path, sizeof path, "%s/combco.%d.a", qrydir, c);
+    if (stat(path, &st) != 0) die("get_species_abundance():%s", path);
+    if (qpos[c][qry_n] * 4 > nid || qpos[c][qry_n] * 2 > (uint64_t)st.st_size) die("get_species_abundance(): component %d is shorter than its index says", c);
+    for (int q = 0; q < qry_n; q++)
+      if (qpos[c][q] > qpos[c][q + 1]) die("get_species_abundance():%s/combco.index.%d does not ascend", qrydir, c);
+  }
+  composite_vec *vec = malloc(8 * ((size_t)ref_n + 1));
+  uint64_t *local = malloc(8 * ((size_t)qry_n + 1)), *row_end = malloc(8 * ((size_t)qry_n + 1));
+  uint32_t *ids = NULL;
+  uint16_t *cnt = NULL;
+  size_t cap = 0;
+  uint64_t batches = 0, hits = 0;
+  double qms = 0.0;
+  for (int q0 = 0; q0 < qry_n;) {
+    int q1 = q0;
+    uint64_t bytes = 0;
+    while (q1 < qry_n) { /* whole samples, at least one */
+      uint64_t b = 0;
+      for (int c = 0; c < comp_num; c++) b += (qpos[c][q1 + 1] - qpos[c][q1]) * 4;
+      if (q1 > q0 && bytes + b > batch_bytes) break;
+      bytes += b;
+      q1++;
+    }
+    const int ns = q1 - q0;
+    if (mk_composite_query_begin(h, (uint32_t)ns) != MK_OK) die("get_species_abundance(): %s", mk_composite_last_error(h));
+    for (int c = 0; c < comp_num; c++) {
+      const uint64_t a = qpos[c][q0], n = qpos[c][q1] - a;
+      if (n > cap) {
+        cap = n + n / 8 + 1024;
+        free(ids); free(cnt);
+        ids = malloc(4 * cap); cnt = malloc(2 * cap);
+        if (!ids || !cnt) die("get_species_abundance(): out of memory");
+      }
+      snprintf(path, sizeof path, "%s/combco.%d", qrydir, c);
+      composite_read_range(path, a * 4, ids, n * 4);
+      snprintf(path, sizeof path, "%s/combco.%d.a", qrydir, c);
+      composite_read_range(path, a * 2, cnt, n * 2);
+      for (int k = 0; k <= ns; k++) local[k] = qpos[c][q0 + k] - a;
+      if (mk_composite_query_component(h, (uint32_t)c, ids, cnt, local) != MK_OK) die("get_species_abundance(): %s", mk_composite_last_error(h));
+    }
+    const mk_composite_row *rows = NULL;
+    if (mk_composite_query_finish(h, &rows, row_end) != MK_OK) die("get_species_abundance(): %s", mk_composite_last_error(h));
+    for (int k = 0; k < ns; k++) {
+      const uint64_t lo = k ? row_end[k - 1] : 0;
+      composite_write_sample(rows + lo, row_end[k] - lo, qryname + (size_t)PATHLEN * (q0 + k), refname, refdir, outdir, binvec, vec);
+    }
+    uint64_t bh = 0, br = 0;
+    double lm = 0.0, qm = 0.0;
+    mk_composite_last_counts(h, &bh, &br);
+    mk_composite_last_kernel_ms(h, &lm, &qm);
+    hits += bh; qms += qm; *load_ms = lm;
+    batches++;
+    q0 = q1;
+  }
+  *batches_out = batches; *hits_out = hits; *query_ms = qms;
+  mk_composite_destroy(h);
+  for (int c = 0; c < comp_num; c++) free(qpos[c]);
+  free(qpos); free(vec); free(local); free(row_end); free(ids); free(cnt);
+}
+
 static int cmd_composite(int argc, char **argv) {
   const char *refdir = NULL, *qrydir = NULL, *outdir = "./";
-  int binvec = 0, device = 0;
+  int binvec = 0, device = 0, route = 0 /* 1 --resident, 2 --per-query */, timing = 0;
+  uint64_t batch_bytes = 256ull << 20; /* query ids of a batch on the resident route */
   for (int i = 0; i < argc; i++)
     if (!strcmp(argv[i], "-d")) { /* cmd_composite(): -d is looked at only without -r (command_composite.c:179-182) */
       int has_r = 0;
@@ -1666,6 +1809,10 @@ static int cmd_composite(int argc, char **argv) {
     else if (!strcmp(argv[i], "-s") && i + 1 < argc) metric = atoi(argv[++i]); /* :83: atoi, as argp hands it over */
     else if (!strncmp(argv[i], "-s", 2) && argv[i][2] && argv[i][2] != '-') metric = atoi(argv[i] + 2); /* -s1, the README's form */
     else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--resident")) route = 1;
+    else if (!strcmp(argv[i], "--per-query")) route = 2;
+    else if (!strcmp(argv[i], "--timing")) timing = 1;
+    else if (!strcmp(argv[i], "--batch-mib") && i + 1 < argc) batch_bytes = strtoull(argv[++i], NULL, 10) << 20; /* test hook: 0 = a sample a batch */
     else if (argv[i][0] != '-') { pos = argv + i; npos = argc - i; break; } /* ARGP_KEY_ARGS: the rest are the query vectors */
     else die("composite option %s is not part of this build (-r -q -i -s -b -o and -d are)", argv[i]);
   }
@@ -1699,13 +1846,28 @@ static int cmd_composite(int argc, char **argv) {
   if (rsn < 32 + (size_t)ref_n * (4 + PATHLEN) || qsn < 32 + (size_t)qry_n * (4 + PATHLEN)) die("get_species_abundance(): truncated cofiles.stat");
   const char *refname = (const char *)rst + 32 + 4 * (size_t)ref_n, *qryname = (const char *)qst + 32 + 4 * (size_t)qry_n;
 
+  /* two routes to the same bytes: the marker database resident on the device and the samples in batches -- the default
+   * from two samples on -- or the reference's loop, one join per sample and component (one sample: strictly less work) */
+  if (route == 1 || (route == 0 && qry_n >= 2)) {
+    uint64_t batches = 0, hits = 0;
+    double load_ms = 0.0, query_ms = 0.0;
+    composite_resident(refdir, qrydir, outdir, binvec, device, ref_n, qry_n, comp_num, refname, qryname, batch_bytes, &batches, &hits, &load_ms, &query_ms);
+    if (timing)
+      printf("{\"composite_timing\": {\"route\": \"resident\", \"samples\": %d, \"batches\": %llu, \"hits\": %llu, \"load_kernel_ms\": %.3f, \"query_kernel_ms\": %.3f}}\n",
+             qry_n, (unsigned long long)batches, (unsigned long long)hits, load_ms, query_ms);
+    free(rst); free(qst);
+    return 0;
+  }
   mk_setop *so;
   if (mk_setop_create(device, &so) != MK_OK) die("mk_setop_create failed: %s", mk_setop_last_error(NULL));
+  uint64_t pq_hits = 0;
+  double pq_join_ms = 0.0;
+  mk_composite_row *prow = malloc(sizeof(mk_composite_row) * ((size_t)ref_n + 1));
   int **vals = calloc((size_t)ref_n, sizeof(int *)); /* per reference sketch: the query's counts of the shared k-mers */
   int *nval = calloc((size_t)ref_n, sizeof(int)), *cap = calloc((size_t)ref_n, sizeof(int));
   uint64_t *seg = malloc(8 * ((size_t)ref_n + 1));
   int *order = malloc(sizeof(int) * (size_t)ref_n), *tmp = malloc(sizeof(int) * (size_t)ref_n);
-  struct { int ref_idx; float pct; } *vec = malloc(8 * ((size_t)ref_n + 1));
+  composite_vec *vec = malloc(8 * ((size_t)ref_n + 1));
 
   for (int q = 0; q < qry_n; q++) {
     for (int r = 0; r < ref_n; r++) nval[r] = 0;
@@ -1733,6 +1895,7 @@ static int cmd_composite(int argc, char **argv) {
       if (mk_setop_join(so, (const uint32_t *)qco + qpos[q], (const uint16_t *)qab + qpos[q], qpos[q + 1] - qpos[q], (const uint32_t *)rco,
                         rpos[ref_n], rpos, (uint32_t)ref_n + 1, &counts, &m, seg) != MK_OK)
         die("get_species_abundance(): %s", mk_setop_last_error(so));
+      if (timing) { double ms = 0.0; mk_setop_last_join_ms(so, &ms); pq_join_ms += ms; pq_hits += m; }
       for (int r = 0; r < ref_n; r++) {
         const int k = (int)(seg[r + 1] - seg[r]);
         if (nval[r] + k > cap[r]) {
@@ -1757,19 +1920,7 @@ static int cmd_composite(int argc, char **argv) {
       }
       memcpy(order, tmp, sizeof(int) * (size_t)ref_n);
     }
-    FILE *vf = NULL;
-    if (binvec) { /* :573-581 */
-      char dir[PATHLEN * 2 + 32], qn[PATHLEN + 1];
-      if (strlen(outdir) < 3) snprintf(dir, sizeof dir, "%s/abundance_Vec", refdir);
-      else snprintf(dir, sizeof dir, "%s", outdir);
-      mkdir(dir, 0777);
-      snprintf(qn, sizeof qn, "%.*s", PATHLEN, qryname + (size_t)PATHLEN * q);
-      const char *base = strrchr(qn, '/');
-      snprintf(path, sizeof path, "%s/%s.abv", dir, base ? base + 1 : qn);
-      if (!(vf = fopen(path, "wb"))) die("get_species_abundance():%s", path);
-    }
-    int num_pass = 0;
-    float vecsum = 0;
+    uint64_t nrows = 0;
     for (int i = 0; i < ref_n; i++) {
       const int r = order[i], kmer_num = nval[r];
       if (kmer_num < 6) break; /* MIN_KM_S */
@@ -1780,24 +1931,14 @@ static int cmd_composite(int argc, char **argv) {
       const int median_idx = kmer_num / 2, pct_idx = kmer_num * 0.98; /* ST_PCTL */
       int lastsum = 0, lastn = 0;
       for (int n = pct_idx; n <= kmer_num * 0.99; n++) { lastsum += v[n]; lastn++; } /* ED_PCTL */
-      if (binvec) {
-        if (v[median_idx] > 1 && kmer_num > 7) {
-          vec[num_pass].ref_idx = r;
-          vec[num_pass].pct = (float)lastsum / lastn;
-          vecsum += vec[num_pass].pct;
-          num_pass++;
-        }
-      } else {
-        printf("%.*s\t%.*s\t%d\t%f\t%f\t%d\t%d\n", PATHLEN, qryname + (size_t)PATHLEN * q, PATHLEN, refname + (size_t)PATHLEN * r, kmer_num,
-               (float)sum / kmer_num, (float)lastsum / lastn, v[median_idx], v[kmer_num]);
-      }
+      prow[nrows++] = (mk_composite_row){(uint32_t)r, kmer_num, sum, lastsum, lastn, v[median_idx], v[kmer_num]};
     }
-    if (vf) {
-      for (int i = 0; i < num_pass; i++) vec[i].pct = (vec[i].pct - 1) * 100 / (vecsum - num_pass);
-      fwrite(vec, 8, (size_t)num_pass, vf);
-      fclose(vf);
-    }
+    composite_write_sample(prow, nrows, qryname + (size_t)PATHLEN * q, refname, refdir, outdir, binvec, vec);
   }
+  if (timing)
+    printf("{\"composite_timing\": {\"route\": \"per-query\", \"samples\": %d, \"batches\": %d, \"hits\": %llu, \"load_kernel_ms\": 0.000, \"query_kernel_ms\": %.3f}}\n",
+           qry_n, qry_n, (unsigned long long)pq_hits, pq_join_ms);
+  free(prow);
   mk_setop_destroy(so);
   for (int r = 0; r < ref_n; r++) free(vals[r]);
   free(vals); free(nval); free(cap); free(seg); free(order); free(tmp); free(vec); free(rst); free(qst);
