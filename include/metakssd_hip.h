@@ -874,6 +874,63 @@ int mk_sketch_batch_begin_gz(mk_engine *e, int mode, const mk_gz_file *files, ui
 /* MK_INFL_* of every file of the batch the LAST mk_sketch_batch_end handed out (zeros when that was not a gz batch) */
 int mk_sketch_batch_gz_status(mk_engine *e, uint32_t *status, uint32_t nfiles);
 
+/* ---- ONE gzip member of any size inflated on the device, many wavefronts a stream (what sequencers, gzip and pigz write as
+ * `.fastq.gz`; opt-in replacement of the `zcat -fc` child in front of the -A reader) -----------------------------
+ * The payload is cut into spans of S compressed bytes.  A finder wave per span looks for the first bit at which a non-final
+ * dynamic block header is valid; span 0 and every such bit start a PIECE.  A wave per piece decodes it to 16-bit symbols without
+ * knowing the 32 KiB of text in front of it (references into them are markers), the 32 KiB windows are handed down the chain of
+ * pieces, the markers are replaced, and the CRC32 and the length of the text are held against the trailer.
+ *   mk_gzip_scan_stream   host: header and trailer of a single-member gzip file of any size
+ *   mk_inflate_stream     device: everything up to the checked text, with a copy back (tests, tools)
+ *   mk_sketch_push_gzip   the same bound to an engine: the text is framed and scanned like mk_sketch_push_bgzf's */
+#define MK_INFL_MISSED 9    /* a piece decoded past the start of the next one: the finder's candidate was no block start */
+#define MK_INFL_CAPACITY 10 /* a piece gave more than R times the compressed bytes it covers */
+/* mk_gzip_scan's rule with two differences: ISIZE, which is only the text's length mod 2^32, has no upper limit and may be 0, and
+ * the payload may be of any length.  A BGZF file and a concatenation of members pass, as they do there: the caller asks
+ * mk_bgzf_scan first, and the decode says MK_INFL_TRAILING.  Host code only. */
+int mk_gzip_scan_stream(int fd, const uint8_t *mem, size_t size, mk_gzip_info *out);
+typedef struct mk_gunzip_opts {
+  uint32_t span_bytes;  /* S: compressed bytes a span; 0 = 128 KiB, at least 64 */
+  uint32_t ratio;       /* R: symbols a piece may give per compressed byte it covers; 0 = 16 */
+  uint32_t batch_spans; /* spans whose pieces are decoded, resolved and framed together; 0 = as many as keep R * S * spans within
+                         * 2 GiB of text (1024 with the defaults), which is also the most */
+  uint32_t reserved;
+} mk_gunzip_opts;
+typedef struct mk_gunzip_piece {
+  uint64_t start_bit; /* in the payload */
+  uint64_t text_len;  /* bytes of text it gave */
+} mk_gunzip_piece;
+typedef struct mk_gunzip_pieces {
+  mk_gunzip_piece *v; /* malloc()ed by mk_inflate_stream, released by mk_gunzip_pieces_free */
+  uint64_t n;
+} mk_gunzip_pieces;
+void mk_gunzip_pieces_free(mk_gunzip_pieces *p);
+/* `comp` (host) is the whole file, `info` what mk_gzip_scan_stream said about it (is_single != 0).  The text goes to text_out
+ * (cap bytes; MK_ERR_ARG when a text without a status is longer, *text_len says how long) and *status says how the decode went: MK_INFL_OK, or the
+ * status of the first piece in stream order that has one (pieces decode in parallel, batch after batch), or, behind the last batch,
+ * MK_INFL_OUTPUT_LEN (the length mod 2^32 is not ISIZE) or MK_INFL_CRC.  With a status the text is not copied back and *text_len is
+ * what was resolved before it.  pieces (may be NULL): every piece decoded so far, in stream order.  Damage is a status, never a
+ * fault: loads stay inside the uploaded payload and its zeroed slack, stores inside a piece's R * (bytes covered) symbols.
+ * The call returns MK_OK whatever the status is. */
+int mk_inflate_stream(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_gzip_info *info, const mk_gunzip_opts *opts,
+                      uint8_t *text_out, size_t cap, uint64_t *text_len, int32_t *status, mk_gunzip_pieces *pieces);
+typedef struct mk_gunzip_stats {
+  uint64_t pieces, batches, comp_bytes, text_bytes, rows;
+  double find_ms, decode_ms, resolve_ms; /* device time of the finder, the decode to symbols, window chain + resolve + CRC */
+  double frame_ms;                       /* ... and of the framing kernels */
+  double t_read_s, t_total_s;            /* host: reading the file into pinned staging, the whole call */
+  int64_t bad_piece;   /* MK_ERR_FORMAT from the decode: the piece's index in the stream (-1: the trailer check, or a long line) */
+  int32_t bad_status;  /* ... and the MK_INFL_* status (0: a line of 4095+ characters) */
+  int32_t reserved;
+} mk_gunzip_stats;
+/* The first `size` bytes behind fd, a file mk_gzip_scan_stream accepts (MK_ERR_ARG otherwise), go into the sketch begun on e with
+ * mk_sketch_begin (the -A reader): batch after batch the text is made as in mk_inflate_stream and framed in slices of at most
+ * 128 MiB with the carry of mk_sketch_push_bgzf; rows and errors are those of mk_fastq_frame over the text with final != 0.
+ * MK_ERR_FORMAT: an inflate status (st->bad_status != 0) or a line of 4095+ characters.  Pieces decode in parallel and the trailer
+ * is checked last, so a status may appear AFTER rows were pushed: the caller finishes and drops the sketch, begins it anew and
+ * reads the file another way.  Engines with MK_OPT_SPLIT_CUS: MK_ERR_STATE.  Error text: mk_bgzf_last_error. */
+int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, uint64_t first_ordinal, mk_gunzip_stats *st);
+
 /* distance.out (host).  Options as command_dist_wrapper.c:83-92. */
 typedef struct mk_dist_opts {
   int32_t metric;     /* -M: 0 Jaccard / MashD, 1 containment / AafD */

@@ -133,6 +133,24 @@ class BgzfStatsC(C.Structure):
                 ("bad_block", C.c_int64), ("bad_status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GunzipOptsC(C.Structure):
+    _fields_ = [("span_bytes", C.c_uint32), ("ratio", C.c_uint32), ("batch_spans", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GunzipPieceC(C.Structure):
+    _fields_ = [("start_bit", C.c_uint64), ("text_len", C.c_uint64)]
+
+
+class GunzipPiecesC(C.Structure):
+    _fields_ = [("v", C.POINTER(GunzipPieceC)), ("n", C.c_uint64)]
+
+
+class GunzipStatsC(C.Structure):
+    _fields_ = [("pieces", C.c_uint64), ("batches", C.c_uint64), ("comp_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("rows", C.c_uint64),
+                ("find_ms", C.c_double), ("decode_ms", C.c_double), ("resolve_ms", C.c_double), ("frame_ms", C.c_double),
+                ("t_read_s", C.c_double), ("t_total_s", C.c_double), ("bad_piece", C.c_int64), ("bad_status", C.c_int32), ("reserved", C.c_int32)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -170,6 +188,10 @@ def _load():
         "mk_sketch_batch_begin_gz": [vp, C.c_int, C.POINTER(GzFileC), u32],
         "mk_sketch_batch_gz_status": [vp, vp, u32],
         "mk_gzip_scan": [C.c_int, vp, C.c_size_t, C.POINTER(GzipInfoC)],
+        "mk_gzip_scan_stream": [C.c_int, vp, C.c_size_t, C.POINTER(GzipInfoC)],
+        "mk_inflate_stream": [vp, vp, C.c_size_t, C.POINTER(GzipInfoC), C.POINTER(GunzipOptsC), vp, C.c_size_t, C.POINTER(u64), C.POINTER(i32),
+                              C.POINTER(GunzipPiecesC)],
+        "mk_sketch_push_gzip": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), u64, C.POINTER(GunzipStatsC)],
         "mk_inflate_members": [vp, vp, C.c_size_t, C.POINTER(GzMemberC), u32, vp, C.c_size_t, C.POINTER(GzMemberResultC)],
         "mk_sketch_finish": [vp, C.POINTER(ResultC)],
         "mk_sketch_finish_begin": [vp],
@@ -292,6 +314,8 @@ def _load():
     lib.mk_bgzf_last_error.restype = C.c_char_p
     lib.mk_bgzf_free.argtypes = [C.POINTER(BgzfBlockC)]
     lib.mk_bgzf_free.restype = None
+    lib.mk_gunzip_pieces_free.argtypes = [C.POINTER(GunzipPiecesC)]
+    lib.mk_gunzip_pieces_free.restype = None
     lib.mk_setop_stream.argtypes = [vp]
     lib.mk_setop_stream.restype = vp
     lib.mk_last_error.argtypes = [vp]
@@ -557,6 +581,21 @@ class Engine:
                 rc = lib.mk_sketch_push_bgzf(self.h, fd, os.fstat(fd).st_size, C.byref(o), first_ordinal, C.byref(st))
             else:
                 rc = lib.mk_sketch_push_bgzf_q(self.h, fd, os.fstat(fd).st_size, C.byref(o), qmin, first_ordinal, C.byref(st))
+        finally:
+            os.close(fd)
+        if rc:
+            err = MkError(rc, (lib.mk_bgzf_last_error() or b"").decode())
+            err.stats = st
+            raise err
+        return st
+
+    def push_gzip(self, path, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0):
+        """a single-member gzip FASTQ file into the sketch in progress (mk_sketch_push_gzip) -> GunzipStatsC; an inflate status or
+        a long line raises MkError(MK_ERR_FORMAT) with the statistics in .stats: the sketch is then to be begun anew"""
+        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, 0), GunzipStatsC()
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            rc = lib.mk_sketch_push_gzip(self.h, fd, os.fstat(fd).st_size, C.byref(o), first_ordinal, C.byref(st))
         finally:
             os.close(fd)
         if rc:
@@ -1197,7 +1236,7 @@ MK_BYREAD_MAX_PUSH = 8 << 20
 
 
 MK_INFL_OK, MK_INFL_BAD_BLOCK, MK_INFL_BAD_LENGTHS, MK_INFL_BAD_CODE, MK_INFL_BAD_DISTANCE, MK_INFL_INPUT, MK_INFL_OUTPUT_LEN, MK_INFL_CRC = range(8)
-MK_INFL_TRAILING = 8
+MK_INFL_TRAILING, MK_INFL_MISSED, MK_INFL_CAPACITY = 8, 9, 10
 MK_CRC_SLICE = 16384
 BGZF_FIELDS = ("in_off", "out_off", "in_len", "pay_off", "pay_len", "crc32", "isize")
 
@@ -1319,6 +1358,25 @@ def gzip_scan(data=None, path=None):
     return {"pay_off": int(info.pay_off), "pay_len": int(info.pay_len), "crc32": int(info.crc32), "isize": int(info.isize)}
 
 
+def gzip_scan_stream(data=None, path=None, raw=False):
+    """mk_gzip_scan_stream over bytes or over a file -> dict(pay_off, pay_len, crc32, isize) (raw: the GzipInfoC), or None when the
+    file is not one gzip member.  Host code: no GPU needed."""
+    info = GzipInfoC()
+    if path is not None:
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            _check(lib.mk_gzip_scan_stream(fd, None, os.fstat(fd).st_size, C.byref(info)))
+        finally:
+            os.close(fd)
+    else:
+        b = np.frombuffer(bytes(data), dtype=np.uint8)
+        _check(lib.mk_gzip_scan_stream(-1, b.ctypes.data if len(b) else C.c_void_p(1), len(b), C.byref(info)))
+    if not info.is_single:
+        assert (info.pay_off, info.pay_len, info.crc32, info.isize) == (0, 0, 0, 0)
+        return None
+    return info if raw else {"pay_off": int(info.pay_off), "pay_len": int(info.pay_len), "crc32": int(info.crc32), "isize": int(info.isize)}
+
+
 class Inflate:
     """BGZF members inflated and FASTQ text framed on the device (mk_inflate_*), with copies back to the host for tests"""
 
@@ -1360,6 +1418,26 @@ class Inflate:
         res = (GzMemberResultC * max(1, n))()
         self._check(lib.mk_inflate_members(self.h, b.ctypes.data if len(b) else None, len(b), arr, n, out.ctypes.data, end, res))
         return out[:end].tobytes(), [(int(r.status), int(r.consumed), int(r.pos), int(r.crc32)) for r in res[:n]]
+
+    def stream(self, comp, span_bytes=0, ratio=0, batch_spans=0, cap=None, guard=64):
+        """mk_inflate_stream over a whole gzip file (bytes) -> (text or None, MK_INFL_* status, [(start bit, text length) per piece],
+        text length).  The text buffer has cap bytes (default: ISIZE, which is the text's length for texts below 4 GiB) between two
+        guards of `guard` bytes, which must come back untouched."""
+        info = gzip_scan_stream(comp, raw=True)
+        if info is None:
+            raise MkError(MK_ERR_ARG, "not a single-member gzip file")
+        b = np.frombuffer(bytes(comp), dtype=np.uint8)
+        cap = int(info.isize) if cap is None else cap
+        buf = np.full(cap + 2 * guard, 0xC3, dtype=np.uint8)
+        o, n, st, pieces = GunzipOptsC(span_bytes, ratio, batch_spans, 0), C.c_uint64(0), C.c_int32(-1), GunzipPiecesC()
+        rc = lib.mk_inflate_stream(self.h, b.ctypes.data, len(b), C.byref(info), C.byref(o), buf.ctypes.data + guard, cap, C.byref(n),
+                                   C.byref(st), C.byref(pieces))
+        table = [(int(pieces.v[i].start_bit), int(pieces.v[i].text_len)) for i in range(pieces.n)]
+        lib.mk_gunzip_pieces_free(C.byref(pieces))
+        self._check(rc)
+        assert (buf[:guard] == 0xC3).all() and (buf[guard + cap:] == 0xC3).all(), "a write outside the text buffer"
+        text = buf[guard:guard + n.value].tobytes() if st.value == 0 else None
+        return text, st.value, table, n.value
 
     def frame(self, text, final=True):
         """mk_fastq_frame_device -> (rows u8 [nrows * stride], stride, nrows, consumed, longest line, rc)"""

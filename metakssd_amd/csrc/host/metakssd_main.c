@@ -156,6 +156,9 @@ static int g_gz_batches = 0;        /* --device-inflate: single-member .gz genom
                                      * children are 6-14 times faster on 1 024 genomes */
 static int g_device_inflate_q = 0;  /* --device-inflate: a BGZF-compressed FASTQ on the -n / -Q reader (dist without -A) is inflated, framed and quality-masked on
                                      * the device (mk_sketch_push_bgzf_q), 11-12 times the zcat pipe on 2 M reads.  Opt-in: without the switch this input keeps zcat */
+static int g_device_gunzip = 0;     /* --device-gunzip: an ordinary single-member .gz FASTQ on the -A reader is inflated by many wavefronts (mk_sketch_push_gzip,
+                                     * DESIGN.md 4.14).  Opt-in: without the switch such a file keeps zcat */
+static mk_gunzip_opts g_gunzip_opts; /* --gunzip-span-bytes, --gunzip-ratio, --gunzip-batch-spans (test hooks; 0 = the library's defaults) */
 static uint64_t g_inflate_chunk_bytes = 0; /* --inflate-chunk-kib: text bytes per chunk of the device route (test hook; 0 = the library's default) */
 static int g_timing = 0; /* --timing */
 static int g_component_sz = 8; /* --component-sz: the reference's compile-time COMPONENT_SZ (global_basic.h:35-37) */
@@ -677,9 +680,47 @@ static int sketch_fastq_bgzf(ctx_t *c, const char *path) {
   return 1;
 }
 
+/* --device-gunzip: a .gz that is ONE gzip member (mk_gzip_scan_stream; a BGZF file has gone its own way before) is inflated, checked
+ * and framed on the device.  0: not such a file, or the device route gave it up with a status -- then what was pushed is finished
+ * and dropped, the caller begins the sketch anew and reads the file from its start through `zcat -fc`, which alone decides whether
+ * the file is damaged; --timing says so ("fallback": the status). */
+static int sketch_fastq_gunzip(ctx_t *c, const char *path) {
+  if (!g_device_gunzip || !c->bgzf_ok || c->occ || g_no_device_inflate || !has_suffix(path, ".gz")) return 0;
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return 0;
+  struct stat st;
+  mk_gzip_info info;
+  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || mk_gzip_scan_stream(fd, NULL, (size_t)st.st_size, &info) != MK_OK || !info.is_single) { close(fd); return 0; }
+  mk_engine *e = sketch_engine(c);
+  if (c->t_first_push == 0) c->t_first_push = now_s() - g_t0;
+  mk_gunzip_stats gs;
+  const int rc = mk_sketch_push_gzip(e, fd, (size_t)st.st_size, &g_gunzip_opts, c->next_ordinal, &gs);
+  close(fd);
+  if (rc == MK_ERR_FORMAT) {
+    mk_result dropped;
+    const int frc = mk_sketch_finish(e, &dropped); /* rows pushed before the status showed: finished and dropped, the next push begins anew */
+    if (frc != MK_OK && frc != MK_ERR_CROWDED) die("mk_sketch_finish failed (%d): %s", frc, mk_last_error(e));
+    if (frc == MK_OK) mk_result_release(e, &dropped);
+    c->begun = 0;
+    g_gz_fallback = gs.bad_status ? mk_inflate_status_text(gs.bad_status) : "long line";
+    return 0;
+  }
+  if (rc != MK_OK) die("mk_sketch_push_gzip failed (%d): %s", rc, mk_bgzf_last_error());
+  c->next_ordinal += gs.rows;
+  c->nrows_total += gs.rows;
+  c->t_last_push = now_s() - g_t0;
+  if (g_timing)
+    printf("{\"input\": \"%s\", \"route\": \"device-gunzip\", \"pieces\": %llu, \"batches\": %llu, \"comp_bytes\": %llu, \"text_bytes\": %llu, \"rows\": %llu, "
+           "\"find_ms\": %.3f, \"decode_ms\": %.3f, \"resolve_ms\": %.3f, \"frame_ms\": %.3f, \"read_s\": %.4f, \"route_total_s\": %.4f}\n",
+           path, (unsigned long long)gs.pieces, (unsigned long long)gs.batches, (unsigned long long)gs.comp_bytes, (unsigned long long)gs.text_bytes,
+           (unsigned long long)gs.rows, gs.find_ms, gs.decode_ms, gs.resolve_ms, gs.frame_ms, gs.t_read_s, gs.t_total_s);
+  return 1;
+}
+
 static void sketch_fastq(ctx_t *c, const char *path) {
   if (sketch_fastq_mapped(c, path)) return;
   if (sketch_fastq_bgzf(c, path)) return;
+  if (sketch_fastq_gunzip(c, path)) return;
   if (is_compressed(path)) report_route(path, "zcat", NULL);
   g_gz_fallback = NULL;
   ensure_buffers(c);
@@ -2827,6 +2868,10 @@ int main(int argc, char **argv) {
     /* --device-inflate: the two opt-in device routes -- single-member .gz genomes in gz batches and a BGZF FASTQ on
      * the -n / -Q reader (4.12); the -A reader's BGZF route needs no switch.  The later of the two switches holds. */
     else if (!strcmp(argv[i], "--device-inflate")) { g_no_device_inflate = 0; g_gz_batches = 1; g_device_inflate_q = 1; }
+    else if (!strcmp(argv[i], "--device-gunzip")) g_device_gunzip = 1; /* dist -A: a single-member .gz FASTQ inflated on the device */
+    else if (!strcmp(argv[i], "--gunzip-span-bytes") && i + 1 < argc) g_gunzip_opts.span_bytes = (uint32_t)atoll(argv[++i]);
+    else if (!strcmp(argv[i], "--gunzip-ratio") && i + 1 < argc) g_gunzip_opts.ratio = (uint32_t)atoll(argv[++i]);
+    else if (!strcmp(argv[i], "--gunzip-batch-spans") && i + 1 < argc) g_gunzip_opts.batch_spans = (uint32_t)atoll(argv[++i]);
     else if (!strcmp(argv[i], "--inflate-chunk-kib") && i + 1 < argc) g_inflate_chunk_bytes = (uint64_t)atoll(argv[++i]) << 10;
     else if (!strcmp(argv[i], "--chunk-mib") && i + 1 < argc) chunk_bytes = (uint64_t)atoi(argv[++i]) << 20;
     else if (!strcmp(argv[i], "--inflight") && i + 1 < argc) inflight = atoi(argv[++i]); /* row buffers queued for copying */

@@ -96,6 +96,8 @@ const char *mk_inflate_status_text(int status) {
     case MK_INFL_OUTPUT_LEN: return "output length not equal to ISIZE";
     case MK_INFL_CRC: return "CRC mismatch";
     case MK_INFL_TRAILING: return "more members behind the first";
+    case MK_INFL_MISSED: return "a piece start that is no block start";
+    case MK_INFL_CAPACITY: return "a piece's text exceeds its capacity";
     default: return "unknown status";
   }
 }

@@ -41,7 +41,9 @@ static size_t mk_gzip_header_end(const uint8_t *p, size_t size) {
   return at;
 }
 
-int mk_gzip_scan(int fd, const uint8_t *mem, size_t size, mk_gzip_info *out) {
+/* stream != 0: mk_gzip_scan_stream's rule -- ISIZE is the text length mod 2^32 and says nothing about the size, and the payload
+ * may be of any length */
+static int mk_gzip_scan_any(int fd, const uint8_t *mem, size_t size, mk_gzip_info *out, int stream) {
   if (!out || (!mem && fd < 0)) return MK_ERR_ARG;
   memset(out, 0, sizeof *out);
   if (size < 10u + 1u + 8u) return MK_OK; /* the fixed header, one byte of deflate, the trailer */
@@ -51,9 +53,9 @@ int mk_gzip_scan(int fd, const uint8_t *mem, size_t size, mk_gzip_info *out) {
     if (p == MAP_FAILED) return MK_ERR_IO;
   }
   const size_t pay = mk_gzip_header_end(p, size);
-  if (pay && size - pay >= 1u + 8u && size - pay - 8u < ((uint64_t)1 << 31)) {
+  if (pay && size - pay >= 1u + 8u && (stream || size - pay - 8u < ((uint64_t)1 << 31))) {
     const uint32_t isize = mk_gz_le32(p + size - 4);
-    if (isize >= 1u && isize <= MK_BATCH_FILE_MAX) {
+    if (stream || (isize >= 1u && isize <= MK_BATCH_FILE_MAX)) {
       out->pay_off = pay;
       out->pay_len = size - pay - 8u;
       out->crc32 = mk_gz_le32(p + size - 8);
@@ -64,3 +66,7 @@ int mk_gzip_scan(int fd, const uint8_t *mem, size_t size, mk_gzip_info *out) {
   if (!mem) munmap((void *)p, size);
   return MK_OK;
 }
+
+int mk_gzip_scan(int fd, const uint8_t *mem, size_t size, mk_gzip_info *out) { return mk_gzip_scan_any(fd, mem, size, out, 0); }
+
+int mk_gzip_scan_stream(int fd, const uint8_t *mem, size_t size, mk_gzip_info *out) { return mk_gzip_scan_any(fd, mem, size, out, 1); }

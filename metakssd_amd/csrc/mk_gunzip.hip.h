@@ -1,0 +1,732 @@
+/* mk_gunzip.hip.h -- ONE gzip member of any size inflated by many wavefronts (part of mk_inflate.hip, which includes it last; gfx950,
+ * wave64, hand-written).  The known two-pass method (pugz, rapidgzip) around this file's decoder:
+ *
+ *   mk_gun_find_kernel     one wave per span of S compressed bytes: the first bit of the span at which a NON-FINAL DYNAMIC block
+ *                          header is valid.  64 lanes test 64 consecutive bit offsets with the cheap tests (the three header bits,
+ *                          HLIT and HDIST <= 29, Kraft's sum over the 3-bit code length lengths, all bits inside the payload); a
+ *                          survivor is tested by the whole wave with the decoder's own header walk and table builder: a complete
+ *                          code length code, lengths without overrun, a code for symbol 256, a complete literal/length code, a
+ *                          distance code the decoder accepts.  Stored and fixed blocks are never candidates.
+ *   mk_gun_decode_kernel   one wave per piece (span 0 and every candidate start one): mk_inflate_kernel's decode with 16-bit output.
+ *                          A literal is its byte; a match source inside the piece is copied symbol by symbol; a source in front of
+ *                          the piece's first symbol is the marker 0x8000 | (32768 + source), source < 0.  In front of every block
+ *                          header the bit position is held against the next piece's start: equal stops the piece, past it is
+ *                          MK_INFL_MISSED.  More symbols than the piece's capacity: MK_INFL_CAPACITY.
+ *   mk_gun_chain_kernel    one workgroup, pieces in order: W(c), the last 32 KiB of the text up to piece c's end, from W(c - 1) and
+ *                          piece c's symbols.  All of a batch's windows are kept: W(c - 1) is what piece c's markers index.
+ *   mk_gun_resolve_kernel  all pieces at once: text[off(c) + i] = sym < 0x8000 ? sym : W(c - 1)[sym & 0x7fff]
+ * The text's CRC32 is mk_crc32_files_kernel's and the combine kernel's over segments of at most 1 GiB, carried from batch to batch
+ * on the host.  Safety: the finder and the decode load inside the uploaded payload and the zeroed slack behind it, a piece stores
+ * inside its cap symbols, the chain inside its windows, the resolve inside the sum of the lengths the decode reported; every loop
+ * consumes input bits or produces output symbols and is bounded by the two sizes.  Bound of each kernel: DESIGN.md 4.14. */
+
+#include <algorithm>
+
+namespace {
+
+#define MK_GUN_WINDOW 32768u
+#define MK_GUN_NONE (~(uint64_t)0)
+#define MK_GUN_SLACK 64u              /* zeroed bytes behind the file's last byte on the device */
+#define MK_GUN_SLICE ((uint64_t)128 << 20) /* text bytes one framing pass takes */
+#define MK_GUN_CRC_SEG ((uint64_t)1 << 30)
+
+typedef mk_bits_t<true> mk_zbits;
+
+struct mk_gun_piece { /* the device's table, one entry a piece of the batch */
+  uint64_t start;    /* bit in the payload */
+  uint64_t end;      /* the next piece's start; MK_GUN_NONE: the stream's last piece */
+  uint64_t sym_off;  /* its symbols in the batch's symbol buffer */
+  uint64_t text_off; /* its text in the batch's text: the host's prefix sum over `len` */
+  uint32_t cap;      /* symbols it may give */
+  uint32_t first;    /* the stream's first piece: nothing lies in front of it */
+  uint32_t status, len; /* left by the decode */
+  uint64_t stop;     /* the bit the decode stopped at */
+};
+
+__device__ __forceinline__ uint64_t mk_uni64(uint64_t v) { return (uint64_t)mk_uni((uint32_t)(v >> 32)) << 32 | mk_uni((uint32_t)v); }
+
+/* the dynamic block header behind BTYPE (b refilled): HLIT, HDIST, HCLEN, the code length code, the lengths into L.lens[0, nl + nd)
+ * -> MK_INFL_*, the same in every lane */
+template <class B>
+__device__ uint32_t mk_dyn_lengths(B &b, mk_infl_lds &L, uint32_t lane, uint32_t &nl, uint32_t &nd) {
+  nl = b.get(5) + 257u;
+  nd = b.get(5) + 1u;
+  const uint32_t nc = b.get(4) + 4u;
+  if (nl > 286u || nd > 30u) return MK_INFL_BAD_LENGTHS;
+  if (lane < 19u) L.lens[320u + lane] = 0;
+  mk_lds_fence();
+  for (uint32_t i = 0; i < nc; i++) {
+    b.refill();
+    const uint32_t v = b.get(3);
+    if (lane == 0u) L.lens[320u + mk_clorder[i]] = (uint8_t)v;
+  }
+  mk_lds_fence();
+  if (mk_build(L.lens + 320, 19u, L.dist_cnt, L.dist_sym, L.dist_tab, 7u, false, lane)) return MK_INFL_BAD_CODE;
+  uint32_t idx = 0, prev = 0;
+  while (idx < nl + nd) {
+    b.refill();
+    if (b.past_end()) return MK_INFL_INPUT;
+    const int s = mk_decode(b, L.dist_tab, 7u, L.dist_cnt, L.dist_sym);
+    if (s < 0) return MK_INFL_BAD_CODE;
+    if (s < 16) {
+      if (lane == 0u) L.lens[idx] = (uint8_t)s;
+      prev = (uint32_t)s;
+      idx++;
+      continue;
+    }
+    uint32_t rep, val = 0;
+    if (s == 16) {
+      if (idx == 0u) return MK_INFL_BAD_LENGTHS;
+      val = prev;
+      rep = 3u + b.get(2);
+    } else if (s == 17) rep = 3u + b.get(3);
+    else rep = 11u + b.get(7);
+    if (idx + rep > nl + nd) return MK_INFL_BAD_LENGTHS;
+    for (uint32_t i = lane; i < rep; i += 64u) L.lens[idx + i] = (uint8_t)val;
+    prev = val;
+    idx += rep;
+  }
+  mk_lds_fence();
+  if (L.lens[256] == 0) return MK_INFL_BAD_LENGTHS;
+  return MK_INFL_OK;
+}
+
+/* b at bit `bit` of the payload; comp is 16-byte aligned and holds the payload from comp + shift on.  Returns 8 * (the byte b's
+ * coordinates start at, in the payload's): payload bit = b.bitpos() + that */
+__device__ __forceinline__ int64_t mk_gun_seek(mk_zbits &b, const uint8_t *comp, uint32_t shift, uint64_t pay_len, uint64_t bit) {
+  const uint64_t base_off = ((uint64_t)shift + (bit >> 3)) & ~(uint64_t)15u;
+  const uint64_t end = (uint64_t)shift + pay_len - base_off;
+  b.base = comp + base_off;
+  b.end = end < 0xfffffff0ull ? (uint32_t)end : 0xfffffff0u; /* (the host gives no piece 2 GiB to cover) */
+  b.seek((uint32_t)((uint64_t)shift + (bit >> 3) - base_off));
+  b.get((uint32_t)bit & 7u);
+  return 8 * ((int64_t)base_off - (int64_t)shift);
+}
+
+/* cand[i]: the candidate of span span0 + i (span0 >= 1), MK_GUN_NONE when the span has none */
+__global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_find_kernel(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len, uint32_t S,
+                                                                          uint64_t span0, uint32_t nspans, uint64_t *cand) {
+  __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t i = blockIdx.x * MK_INFL_WAVES + wave;
+  if (i >= nspans) return;
+  mk_infl_lds &L = lds_all[wave];
+  const uint64_t c = span0 + i, nbits = 8u * pay_len;
+  const uint64_t lo = 8u * c * S, hi = 8u * (c + 1u) * S < nbits ? 8u * (c + 1u) * S : nbits;
+  const uint32_t *words = (const uint32_t *)comp;
+  uint64_t found = MK_GUN_NONE;
+  for (uint64_t p0 = lo; p0 < hi && found == MK_GUN_NONE; p0 += 64u) {
+    const uint64_t p = p0 + lane;
+    bool ok = false;
+    if (p < hi) { /* 128 bits from bit p on: four aligned words, inside the payload, its trailer and the slack */
+      const uint64_t q = p + 8u * shift;
+      const uint64_t w = q >> 5;
+      const uint32_t sh = (uint32_t)q & 31u;
+      const uint64_t a = (uint64_t)words[w] | (uint64_t)words[w + 1u] << 32, bq = (uint64_t)words[w + 2u] | (uint64_t)words[w + 3u] << 32;
+      const uint64_t v0 = sh ? a >> sh | bq << (64u - sh) : a, v1 = bq >> sh;
+      const uint32_t h = (uint32_t)v0;
+      const uint32_t nc = ((h >> 13) & 15u) + 4u;
+      if ((h & 7u) == 4u && ((h >> 3) & 31u) <= 29u && ((h >> 8) & 31u) <= 29u && p + 17u + 3u * nc <= nbits) {
+        const uint64_t t0 = v0 >> 17, t1 = v0 >> 62 | v1 << 2; /* triples 0..14, triples 15..18 */
+        uint32_t kraft = 0;
+        for (uint32_t k = 0; k < 19u; k++) {
+          const uint32_t n = (uint32_t)(k < 15u ? t0 >> (3u * k) : t1 >> (3u * (k - 15u))) & 7u;
+          if (k < nc && n) kraft += 128u >> n;
+        }
+        ok = kraft == 128u;
+      }
+    }
+    uint64_t m = __ballot(ok);
+    while (m && found == MK_GUN_NONE) { /* the survivors, lowest bit first, each by the whole wave */
+      const uint64_t cp = p0 + (uint64_t)__builtin_ctzll(m);
+      m &= m - 1ull;
+      mk_zbits b;
+      b.win = L.win;
+      b.lane = lane;
+      mk_gun_seek(b, comp, shift, pay_len, cp);
+      b.refill();
+      b.get(3);
+      uint32_t nl = 0, nd = 0;
+      if (mk_dyn_lengths(b, L, lane, nl, nd) || b.past_end()) continue;
+      if (mk_build(L.lens, nl, L.lit_cnt, L.lit_sym, L.lit_tab, MK_INFL_LBITS, false, lane)) continue;
+      if (mk_build(L.lens + nl, nd, L.dist_cnt, L.dist_sym, L.dist_tab, MK_INFL_DBITS, true, lane)) continue;
+      found = cp;
+    }
+  }
+  if (lane == 0u) cand[i] = found;
+}
+
+__global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len,
+                                                                            mk_gun_piece *pieces, uint32_t npieces, uint16_t *syms) {
+  __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t k = blockIdx.x * MK_INFL_WAVES + wave;
+  if (k >= npieces) return;
+  mk_infl_lds &L = lds_all[wave];
+  const uint64_t start = mk_uni64(pieces[k].start), end_bit = mk_uni64(pieces[k].end);
+  const uint32_t cap = mk_uni(pieces[k].cap), back = mk_uni(pieces[k].first) ? 0u : MK_GUN_WINDOW;
+  const bool last_piece = end_bit == MK_GUN_NONE;
+  uint16_t *out = syms + mk_uni64(pieces[k].sym_off);
+  mk_zbits b;
+  b.win = L.win;
+  b.lane = lane;
+  const int64_t bit0 = mk_gun_seek(b, comp, shift, pay_len, start);
+
+  uint32_t st = MK_INFL_OK, pos = 0, nlit = 0, synced = 0, lit = 0;
+  auto flush = [&]() { /* pending literals -> one store (they were counted against cap when they came) */
+    if (nlit) {
+      if (lane < nlit) out[pos + lane] = (uint16_t)lit;
+      pos += nlit;
+      nlit = 0;
+    }
+  };
+  for (;;) {
+    b.refill();
+    if (!last_piece) {
+      const uint64_t at = (uint64_t)((int64_t)b.bitpos() + bit0);
+      if (at == end_bit) break;
+      if (at > end_bit) { st = MK_INFL_MISSED; break; }
+    }
+    if (b.past_end()) { st = MK_INFL_INPUT; break; }
+    const uint32_t last = b.get(1), type = b.get(2);
+    if (type == 0u) {
+      b.get(b.cnt & 7u);
+      b.refill();
+      const uint32_t len = b.get(16), nlen = b.get(16);
+      if ((len ^ nlen) != 0xffffu) { st = MK_INFL_BAD_BLOCK; break; }
+      const uint32_t a0 = (uint32_t)(b.bitpos() >> 3);
+      if (b.past_end() || a0 + len > b.end) { st = MK_INFL_INPUT; break; }
+      if (pos + nlit + len > cap) { st = MK_INFL_CAPACITY; break; }
+      flush();
+      for (uint32_t i = lane; i < len; i += 64u) out[pos + i] = (uint16_t)b.base[a0 + i];
+      pos += len;
+      b.seek(a0 + len);
+    } else if (type == 3u) {
+      st = MK_INFL_BAD_BLOCK;
+      break;
+    } else {
+      uint32_t nl = 288u, nd = 32u;
+      if (type == 1u) {
+        for (uint32_t i = lane; i < 320u; i += 64u) L.lens[i] = (uint8_t)(i < 144u ? 8u : i < 256u ? 9u : i < 280u ? 7u : i < 288u ? 8u : 5u);
+        mk_lds_fence();
+      } else {
+        st = mk_dyn_lengths(b, L, lane, nl, nd);
+        if (st) break;
+      }
+      if (mk_build(L.lens, nl, L.lit_cnt, L.lit_sym, L.lit_tab, MK_INFL_LBITS, true, lane) ||
+          mk_build(L.lens + nl, nd, L.dist_cnt, L.dist_sym, L.dist_tab, MK_INFL_DBITS, true, lane)) { st = MK_INFL_BAD_CODE; break; }
+      for (;;) { /* the tokens of this block: each takes at least one bit of input */
+        b.refill();
+        if (b.past_end()) { st = MK_INFL_INPUT; break; }
+        int s = mk_decode(b, L.lit_tab, MK_INFL_LBITS, L.lit_cnt, L.lit_sym);
+        if (s < 0) { st = MK_INFL_BAD_CODE; break; }
+        if (s < 256) {
+          if (pos + nlit + 1u > cap) { st = MK_INFL_CAPACITY; break; }
+          if (lane == nlit) lit = (uint32_t)s;
+          if (++nlit == 64u) flush();
+          continue;
+        }
+        if (s == 256) break;
+        s -= 257;
+        if (s >= 29) { st = MK_INFL_BAD_CODE; break; }
+        const uint32_t len = (uint32_t)mk_lbase[s] + b.get(mk_lext[s]);
+        b.refill();
+        const int d = mk_decode(b, L.dist_tab, MK_INFL_DBITS, L.dist_cnt, L.dist_sym);
+        if (d < 0) { st = MK_INFL_BAD_CODE; break; }
+        if (d >= 30) { st = MK_INFL_BAD_DISTANCE; break; }
+        const uint32_t dist = (uint32_t)mk_dbase[d] + b.get(mk_dext[d]);
+        flush();
+        if (dist > pos + back) { st = MK_INFL_BAD_DISTANCE; break; }
+        if (pos + len > cap) { st = MK_INFL_CAPACITY; break; }
+        const int32_t from = (int32_t)pos - (int32_t)dist; /* >= -32768; pos < 2^31 */
+        if (from + (int32_t)(len < dist ? len : dist) > (int32_t)synced) { mk_store_fence(); synced = pos; } /* the source was written since the last wait */
+        for (uint32_t i = lane; i < len; i += 64u) {
+          const int32_t src = from + (int32_t)(dist >= len ? i : i % dist);
+          out[pos + i] = src < 0 ? (uint16_t)(0x8000u | (uint32_t)((int32_t)MK_GUN_WINDOW + src)) : out[src];
+        }
+        pos += len;
+      }
+      if (st) break;
+    }
+    if (last) {
+      if (b.past_end()) st = MK_INFL_INPUT;
+      else if (!last_piece || (((uint64_t)((int64_t)b.bitpos() + bit0) + 7u) >> 3) < pay_len) st = MK_INFL_TRAILING;
+      break;
+    }
+  }
+  flush();
+  if (lane == 0u) {
+    pieces[k].status = st;
+    pieces[k].len = pos;
+    pieces[k].stop = (uint64_t)((int64_t)b.bitpos() + bit0);
+  }
+}
+
+/* win: npieces + 1 windows of 32 KiB; window 0 is W of the piece in front of the batch, window c + 1 becomes W(piece c) */
+__global__ void __launch_bounds__(1024) mk_gun_chain_kernel(const mk_gun_piece *__restrict__ pieces, uint32_t npieces, const uint16_t *__restrict__ syms, uint8_t *win) {
+  const uint32_t t = threadIdx.x;
+  for (uint32_t c = 0; c < npieces; c++) {
+    const uint32_t n = pieces[c].len;
+    const uint16_t *s = syms + pieces[c].sym_off;
+    const uint8_t *wp = win + (uint64_t)c * MK_GUN_WINDOW;
+    uint8_t *wn = win + (uint64_t)(c + 1u) * MK_GUN_WINDOW;
+    const uint32_t keep = n < MK_GUN_WINDOW ? MK_GUN_WINDOW - n : 0u; /* bytes of W(c - 1) that stay */
+    for (uint32_t j = t; j < MK_GUN_WINDOW; j += 1024u) {
+      uint32_t v;
+      if (j < keep) v = wp[j + n];
+      else {
+        const uint32_t sym = s[n - (MK_GUN_WINDOW - j)]; /* j >= keep: n + j >= 32768 */
+        v = sym < 0x8000u ? sym : wp[sym & 0x7fffu];
+      }
+      wn[j] = (uint8_t)v;
+    }
+    __syncthreads(); /* the workgroup's stores to W(c) are visible to its loads in the next turn */
+  }
+}
+
+/* blockIdx.y: the piece */
+__global__ void __launch_bounds__(256) mk_gun_resolve_kernel(const mk_gun_piece *__restrict__ pieces, const uint16_t *__restrict__ syms,
+                                                             const uint8_t *__restrict__ win, uint8_t *text) {
+  const uint32_t c = blockIdx.y, n = pieces[c].len;
+  const uint16_t *s = syms + pieces[c].sym_off;
+  const uint8_t *w = win + (uint64_t)c * MK_GUN_WINDOW;
+  uint8_t *out = text + pieces[c].text_off;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+    const uint32_t sym = s[i];
+    out[i] = (uint8_t)(sym < 0x8000u ? sym : w[sym & 0x7fffu]);
+  }
+}
+
+/* ---- host ------------------------------------------------------------------------------------------------------------------- */
+static uint32_t mk_crc_mul_host(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+  for (uint32_t m = 1u << 31; m; m >>= 1) {
+    if (a & m) p ^= b;
+    b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
+  }
+  return p;
+}
+/* the CRC32 of A || B from the CRC32s of A and B and B's length */
+static uint32_t mk_crc_concat(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  uint32_t p = 1u << 31, sq = 0x00800000u; /* x^0, x^8 */
+  for (uint64_t n = len_b; n; n >>= 1) {
+    if (n & 1u) p = mk_crc_mul_host(sq, p);
+    sq = mk_crc_mul_host(sq, sq);
+  }
+  return mk_crc_mul_host(p, crc_a) ^ crc_b;
+}
+
+struct mk_gun_result {
+  int32_t status = MK_INFL_OK;
+  int64_t bad_piece = -1;
+  uint64_t text_len = 0, npieces = 0, nbatches = 0;
+  double find_ms = 0, decode_ms = 0, resolve_ms = 0, t_read_s = 0;
+};
+
+template <class T>
+static hipError_t mk_gun_grow(T **p, uint64_t *cap, uint64_t need, bool pinned = false) {
+  if (need == 0) need = 1;
+  if (*p && need <= *cap) return hipSuccess;
+  if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); }
+  *p = nullptr; *cap = 0;
+  const uint64_t c = need + need / 8 + 256;
+  const hipError_t r = pinned ? mk_pin_alloc(p, c * sizeof(T), hipHostMallocDefault) : mk_dev_alloc(p, c * sizeof(T));
+  if (r == hipSuccess) *cap = c;
+  return r;
+}
+
+struct mk_gun_run { /* everything the stream decode allocates, released on every way out */
+  hipStream_t S = nullptr, copy = nullptr;
+  uint8_t *h_stage[2] = {nullptr, nullptr}, *d_comp = nullptr, *d_win = nullptr, *d_wcarry = nullptr, *d_text = nullptr;
+  uint64_t *d_cand = nullptr, *h_cand = nullptr;
+  mk_gun_piece *d_pieces = nullptr, *h_pieces = nullptr;
+  uint16_t *d_syms = nullptr;
+  uint8_t *d_crctab = nullptr, *h_crctab = nullptr;
+  uint32_t *d_crcwork = nullptr, *h_crc = nullptr;
+  uint64_t cand_cap = 0, hcand_cap = 0, pieces_cap = 0, hpieces_cap = 0, syms_cap = 0, win_cap = 0, text_cap = 0, crctab_cap = 0, hcrctab_cap = 0, crcwork_cap = 0, hcrc_cap = 0;
+  hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  char err[256] = {0};
+  ~mk_gun_run() {
+    for (int s = 0; s < 2; s++) { if (h_stage[s]) (void)hipHostFree(h_stage[s]); if (ev_up[s]) (void)hipEventDestroy(ev_up[s]); }
+    void *dev[] = {d_comp, d_win, d_wcarry, d_text, d_cand, d_pieces, d_syms, d_crctab, d_crcwork};
+    for (void *p : dev) (void)hipFree(p);
+    void *pin[] = {h_cand, h_pieces, h_crctab, h_crc};
+    for (void *p : pin) if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : ev_t) if (e) (void)hipEventDestroy(e);
+    if (copy) (void)hipStreamDestroy(copy);
+  }
+};
+
+#define MK_GUN_HIP(call)                                                                                   \
+  do {                                                                                                     \
+    hipError_t _r = (call);                                                                                \
+    if (_r != hipSuccess) {                                                                                \
+      snprintf(R.err, sizeof R.err, "%s: %s", #call, hipGetErrorString(_r));                               \
+      (void)hipStreamSynchronize(R.S);                                                                     \
+      if (R.copy) (void)hipStreamSynchronize(R.copy);                                                      \
+      return MK_ERR_HIP;                                                                                   \
+    }                                                                                                      \
+  } while (0)
+
+struct mk_gun_geom { uint32_t S, ratio, batch; };
+static mk_gun_geom mk_gun_geometry(const mk_gunzip_opts *o) {
+  mk_gun_geom g;
+  g.S = o && o->span_bytes ? o->span_bytes : 128u << 10;
+  if (g.S < 64u) g.S = 64u;
+  if (g.S > (1u << 30)) g.S = 1u << 30;
+  g.ratio = o && o->ratio ? o->ratio : 16u;
+  if (g.ratio > 65536u) g.ratio = 65536u;
+  uint64_t most = ((uint64_t)1 << 31) / ((uint64_t)g.ratio * g.S); /* R * S * spans <= 2 GiB of text a batch */
+  if (most < 1u) most = 1u;
+  if (most > 32768u) most = 32768u; /* (a piece per span at most: the resolve grid's second dimension) */
+  g.batch = o && o->batch_spans && o->batch_spans < most ? o->batch_spans : (uint32_t)most;
+  return g;
+}
+
+/* The stream behind `info` of a file of `size` bytes that `read(offset, n, dst)` hands out, on R.S of the current device.  Batch
+ * after batch sink(d_text, n, final) gets the resolved text: n bytes at d_text + MK_FQ_CARRY (a buffer of whole tiles with
+ * MK_FQ_CARRY bytes of room in front), valid until it returns; it returns MK_OK or an error that ends the run.  pieces_out (may be
+ * null): every piece decoded.  MK_OK with res.status set when the decode met a status; the trailer is checked behind the last batch. */
+template <class Read, class Sink>
+static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info, const mk_gunzip_opts *opts, Read read, Sink sink,
+                         std::vector<mk_gunzip_piece> *pieces_out, mk_gun_result &res) {
+  const mk_gun_geom G = mk_gun_geometry(opts);
+  const uint64_t pay_len = info.pay_len, f0 = info.pay_off & ~(uint64_t)15u, total = size - f0; /* the device holds file bytes [f0, size) */
+  const uint32_t shift = (uint32_t)(info.pay_off - f0), S = G.S;
+  if (!info.is_single || info.pay_off + pay_len + 8u != size || pay_len == 0) { snprintf(R.err, sizeof R.err, "not a single-member gzip file"); return MK_ERR_ARG; }
+  const uint64_t NS = (pay_len + S - 1) / S, NB = (NS + G.batch - 1) / G.batch;
+  const uint64_t stage_bytes = std::min<uint64_t>(std::max<uint64_t>((uint64_t)G.batch * S, 65536u), (uint64_t)32 << 20);
+  MK_GUN_HIP(hipStreamCreateWithFlags(&R.copy, hipStreamNonBlocking));
+  for (int s = 0; s < 2; s++) {
+    if (s == 1 && total <= stage_bytes) break;
+    MK_GUN_HIP(mk_pin_alloc(&R.h_stage[s], stage_bytes, hipHostMallocDefault));
+    MK_GUN_HIP(hipEventCreateWithFlags(&R.ev_up[s], hipEventDisableTiming));
+  }
+  for (int k = 0; k < 6; k++) MK_GUN_HIP(hipEventCreate(&R.ev_t[k]));
+  MK_GUN_HIP(mk_dev_alloc(&R.d_comp, total + MK_GUN_SLACK));
+  MK_GUN_HIP(mk_dev_alloc(&R.d_wcarry, (size_t)MK_GUN_WINDOW));
+  MK_GUN_HIP(hipMemsetAsync(R.d_comp + total, 0, MK_GUN_SLACK, R.S));
+  MK_GUN_HIP(hipMemsetAsync(R.d_wcarry, 0, MK_GUN_WINDOW, R.S)); /* a reference in front of the text's first byte reads zeros: the CRC tells */
+
+  uint64_t up = 0, nup = 0;
+  /* file bytes [f0, f0 + upto) are on their way, and R.S waits for them */
+  auto ensure_uploaded = [&](uint64_t upto) -> int {
+    if (upto > total) upto = total;
+    while (up < upto) {
+      const int s = R.h_stage[1] ? (int)(nup & 1u) : 0;
+      const uint64_t n = std::min<uint64_t>(stage_bytes, total - up);
+      if (nup >= (R.h_stage[1] ? 2u : 1u)) MK_GUN_HIP(hipEventSynchronize(R.ev_up[s]));
+      const double t0 = mk_now_s();
+      const int rc = read(f0 + up, n, R.h_stage[s]);
+      res.t_read_s += mk_now_s() - t0;
+      if (rc) { snprintf(R.err, sizeof R.err, "reading the file failed"); (void)hipStreamSynchronize(R.S); (void)hipStreamSynchronize(R.copy); return rc; }
+      MK_GUN_HIP(hipMemcpyAsync(R.d_comp + up, R.h_stage[s], n, hipMemcpyHostToDevice, R.copy));
+      MK_GUN_HIP(hipEventRecord(R.ev_up[s], R.copy));
+      MK_GUN_HIP(hipStreamWaitEvent(R.S, R.ev_up[s], 0));
+      up += n;
+      nup++;
+    }
+    return MK_OK;
+  };
+
+  std::vector<uint64_t> starts(1, 0); /* every piece start known so far, ascending */
+  uint64_t found = 0;                 /* batches whose candidates are known */
+  auto find_batch = [&](uint64_t j) -> int {
+    const uint64_t c0 = std::max<uint64_t>(1, j * G.batch), c1 = std::min<uint64_t>(NS, (j + 1) * G.batch);
+    if (c1 <= c0) return MK_OK;
+    const uint32_t n = (uint32_t)(c1 - c0);
+    int rc = ensure_uploaded(shift + c1 * S + 4096u); /* (a header that starts in the span's last bits ends within 2.3 KB) */
+    if (rc) return rc;
+    MK_GUN_HIP(mk_gun_grow(&R.d_cand, &R.cand_cap, n));
+    MK_GUN_HIP(mk_gun_grow(&R.h_cand, &R.hcand_cap, n, true));
+    MK_GUN_HIP(hipEventRecord(R.ev_t[0], R.S));
+    hipLaunchKernelGGL(mk_gun_find_kernel, dim3((n + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, R.S, (const uint8_t *)R.d_comp, shift, pay_len, S, c0, n, R.d_cand);
+    MK_GUN_HIP(hipGetLastError());
+    MK_GUN_HIP(hipEventRecord(R.ev_t[1], R.S));
+    MK_GUN_HIP(hipMemcpyAsync(R.h_cand, R.d_cand, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, R.S));
+    MK_GUN_HIP(hipStreamSynchronize(R.S));
+    float ms = 0.f;
+    MK_GUN_HIP(hipEventElapsedTime(&ms, R.ev_t[0], R.ev_t[1]));
+    res.find_ms += ms;
+    for (uint32_t i = 0; i < n; i++) if (R.h_cand[i] != MK_GUN_NONE) starts.push_back(R.h_cand[i]);
+    return MK_OK;
+  };
+
+  uint64_t idx = 0; /* the first piece that has not been decoded */
+  uint32_t crc = 0;
+  for (uint64_t bt = 0; bt < NB && idx < starts.size(); bt++) {
+    int rc;
+    while (found < std::min<uint64_t>(NB, bt + 1)) { rc = find_batch(found++); if (rc) return rc; }
+    const uint64_t bit_end = 8u * (bt + 1) * G.batch * S; /* pieces that start in front of this bit are the batch's */
+    uint64_t idx_end = idx;
+    while (idx_end < starts.size() && starts[idx_end] < bit_end) idx_end++;
+    if (idx_end == idx) continue;
+    while (idx_end == starts.size() && found < NB) { rc = find_batch(found++); if (rc) return rc; } /* where the batch's last piece ends */
+    const uint32_t np = (uint32_t)(idx_end - idx);
+    const bool final = idx_end == starts.size();
+    MK_GUN_HIP(mk_gun_grow(&R.h_pieces, &R.hpieces_cap, np, true));
+    MK_GUN_HIP(mk_gun_grow(&R.d_pieces, &R.pieces_cap, np));
+    uint64_t nsyms = 0;
+    for (uint32_t k = 0; k < np; k++) {
+      mk_gun_piece &P = R.h_pieces[k];
+      memset(&P, 0, sizeof P);
+      P.start = starts[idx + k];
+      P.end = idx + k + 1 < starts.size() ? starts[idx + k + 1] : MK_GUN_NONE;
+      const uint64_t covered = (P.end == MK_GUN_NONE ? pay_len : (P.end + 7u) >> 3) - (P.start >> 3);
+      const uint64_t cap = (uint64_t)G.ratio * covered;
+      if (cap >= ((uint64_t)1 << 31) || nsyms + cap >= ((uint64_t)1 << 32)) { /* no candidate for too long: one wave would decode gigabytes */
+        (void)hipStreamSynchronize(R.S); (void)hipStreamSynchronize(R.copy);
+        res.status = MK_INFL_CAPACITY; res.bad_piece = (int64_t)(idx + k);
+        return MK_OK;
+      }
+      P.cap = (uint32_t)cap;
+      P.first = idx + k == 0;
+      P.sym_off = nsyms;
+      nsyms += (cap + 7u) & ~(uint64_t)7u;
+    }
+    MK_GUN_HIP(mk_gun_grow(&R.d_syms, &R.syms_cap, nsyms));
+    MK_GUN_HIP(mk_gun_grow(&R.d_win, &R.win_cap, ((uint64_t)np + 1u) * MK_GUN_WINDOW));
+    rc = ensure_uploaded(R.h_pieces[np - 1].end == MK_GUN_NONE ? total : shift + (R.h_pieces[np - 1].end >> 3) + 4096u);
+    if (rc) return rc;
+    MK_GUN_HIP(hipMemcpyAsync(R.d_pieces, R.h_pieces, (size_t)np * sizeof(mk_gun_piece), hipMemcpyHostToDevice, R.S));
+    MK_GUN_HIP(hipEventRecord(R.ev_t[2], R.S));
+    hipLaunchKernelGGL(mk_gun_decode_kernel, dim3((np + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, R.S, (const uint8_t *)R.d_comp, shift, pay_len, R.d_pieces, np, R.d_syms);
+    MK_GUN_HIP(hipGetLastError());
+    MK_GUN_HIP(hipEventRecord(R.ev_t[3], R.S));
+    MK_GUN_HIP(hipMemcpyAsync(R.h_pieces, R.d_pieces, (size_t)np * sizeof(mk_gun_piece), hipMemcpyDeviceToHost, R.S));
+    MK_GUN_HIP(hipStreamSynchronize(R.S));
+    float ms = 0.f;
+    MK_GUN_HIP(hipEventElapsedTime(&ms, R.ev_t[2], R.ev_t[3]));
+    res.decode_ms += ms;
+    res.nbatches++;
+    uint64_t ntext = 0;
+    for (uint32_t k = 0; k < np; k++) {
+      mk_gun_piece &P = R.h_pieces[k];
+      if (pieces_out) pieces_out->push_back(mk_gunzip_piece{P.start, P.len});
+      res.npieces++;
+      if (P.status) {
+        (void)hipStreamSynchronize(R.copy);
+        res.status = (int32_t)P.status; res.bad_piece = (int64_t)(idx + k);
+        return MK_OK;
+      }
+      if (P.len > P.cap) { snprintf(R.err, sizeof R.err, "piece %llu reports more symbols than its capacity", (unsigned long long)(idx + k)); return MK_ERR_HIP; }
+      P.text_off = MK_FQ_CARRY + ntext;
+      ntext += P.len;
+    }
+    /* chain, resolve, CRC */
+    const uint32_t nseg = (uint32_t)((ntext + MK_GUN_CRC_SEG - 1) / MK_GUN_CRC_SEG);
+    MK_GUN_HIP(mk_gun_grow(&R.d_text, &R.text_cap, mk_fq_buf_bytes(MK_FQ_CARRY + ntext)));
+    MK_GUN_HIP(hipMemcpyAsync(R.d_pieces, R.h_pieces, (size_t)np * sizeof(mk_gun_piece), hipMemcpyHostToDevice, R.S));
+    MK_GUN_HIP(hipMemcpyAsync(R.d_win, R.d_wcarry, MK_GUN_WINDOW, hipMemcpyDeviceToDevice, R.S));
+    MK_GUN_HIP(hipEventRecord(R.ev_t[4], R.S));
+    hipLaunchKernelGGL(mk_gun_chain_kernel, dim3(1), dim3(1024), 0, R.S, (const mk_gun_piece *)R.d_pieces, np, (const uint16_t *)R.d_syms, R.d_win);
+    hipLaunchKernelGGL(mk_gun_resolve_kernel, dim3(64, np), dim3(256), 0, R.S, (const mk_gun_piece *)R.d_pieces, (const uint16_t *)R.d_syms, (const uint8_t *)R.d_win, R.d_text);
+    MK_GUN_HIP(hipGetLastError());
+    MK_GUN_HIP(hipMemcpyAsync(R.d_wcarry, R.d_win + (uint64_t)np * MK_GUN_WINDOW, MK_GUN_WINDOW, hipMemcpyDeviceToDevice, R.S));
+    uint32_t nslices = 0;
+    if (nseg) {
+      const size_t tab_bytes = mk_gz_table_bytes(nseg);
+      MK_GUN_HIP(mk_gun_grow(&R.h_crctab, &R.hcrctab_cap, tab_bytes, true));
+      MK_GUN_HIP(mk_gun_grow(&R.d_crctab, &R.crctab_cap, tab_bytes));
+      mk_infl_blk *tab = (mk_infl_blk *)R.h_crctab;
+      uint32_t *slice0s = (uint32_t *)(R.h_crctab + mk_gz_slice0_at(nseg));
+      for (uint32_t f = 0; f < nseg; f++) {
+        const uint64_t at = (uint64_t)f * MK_GUN_CRC_SEG, n = std::min<uint64_t>(MK_GUN_CRC_SEG, ntext - at);
+        tab[f] = mk_infl_blk{0u, 0u, (uint32_t)(MK_FQ_CARRY + at), (uint32_t)n, 0u};
+        slice0s[f] = nslices;
+        nslices += mk_gz_slices((uint32_t)n);
+      }
+      slice0s[nseg] = nslices;
+      /* the work words: status[nseg] (zeros) | crc[nseg] | slice registers[nslices] */
+      MK_GUN_HIP(mk_gun_grow(&R.d_crcwork, &R.crcwork_cap, 2u * (uint64_t)nseg + nslices));
+      MK_GUN_HIP(mk_gun_grow(&R.h_crc, &R.hcrc_cap, nseg, true));
+      MK_GUN_HIP(hipMemcpyAsync(R.d_crctab, R.h_crctab, tab_bytes, hipMemcpyHostToDevice, R.S));
+      MK_GUN_HIP(hipMemsetAsync(R.d_crcwork, 0, (size_t)nseg * sizeof(uint32_t), R.S));
+      const mk_infl_blk *d_tab = (const mk_infl_blk *)R.d_crctab;
+      const uint32_t *d_slice0s = (const uint32_t *)(R.d_crctab + mk_gz_slice0_at(nseg));
+      hipLaunchKernelGGL(mk_crc32_files_kernel, dim3((nslices + 3u) / 4u), dim3(256), 0, R.S, (const uint8_t *)R.d_text, d_tab, d_slice0s, nseg, nslices, R.d_crcwork + 2u * (size_t)nseg);
+      hipLaunchKernelGGL(mk_crc32_combine_kernel, dim3((nseg + 63u) / 64u), dim3(64), 0, R.S, d_tab, d_slice0s, nseg, (const uint32_t *)(R.d_crcwork + 2u * (size_t)nseg), R.d_crcwork, R.d_crcwork + nseg);
+      MK_GUN_HIP(hipGetLastError());
+      MK_GUN_HIP(hipMemcpyAsync(R.h_crc, R.d_crcwork + nseg, (size_t)nseg * sizeof(uint32_t), hipMemcpyDeviceToHost, R.S));
+    }
+    MK_GUN_HIP(hipEventRecord(R.ev_t[5], R.S));
+    if (!final) { rc = ensure_uploaded(shift + (bt + 3) * G.batch * S + 4096u); if (rc) return rc; } /* the next batches' bytes travel beside this one's work */
+    rc = sink(R.d_text, ntext, final);
+    if (rc) { (void)hipStreamSynchronize(R.S); (void)hipStreamSynchronize(R.copy); return rc; }
+    MK_GUN_HIP(hipStreamSynchronize(R.S));
+    MK_GUN_HIP(hipEventElapsedTime(&ms, R.ev_t[4], R.ev_t[5]));
+    res.resolve_ms += ms;
+    for (uint32_t f = 0; f < nseg; f++) {
+      const uint64_t n = std::min<uint64_t>(MK_GUN_CRC_SEG, ntext - (uint64_t)f * MK_GUN_CRC_SEG);
+      crc = mk_crc_concat(crc, R.h_crc[f], n);
+    }
+    res.text_len += ntext;
+    idx = idx_end;
+  }
+  MK_GUN_HIP(hipStreamSynchronize(R.S));
+  MK_GUN_HIP(hipStreamSynchronize(R.copy));
+  if ((uint32_t)res.text_len != info.isize) res.status = MK_INFL_OUTPUT_LEN;
+  else if (crc != info.crc32) res.status = MK_INFL_CRC;
+  return MK_OK;
+}
+
+} /* namespace */
+
+extern "C" void mk_gunzip_pieces_free(mk_gunzip_pieces *p) {
+  if (!p) return;
+  free(p->v);
+  p->v = nullptr;
+  p->n = 0;
+}
+
+extern "C" int mk_inflate_stream(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_gzip_info *info, const mk_gunzip_opts *opts,
+                                 uint8_t *text_out, size_t cap, uint64_t *text_len, int32_t *status, mk_gunzip_pieces *pieces) {
+  if (!h || !comp || !info || !text_len || !status || (!text_out && cap)) return MK_ERR_ARG;
+  *text_len = 0;
+  *status = MK_INFL_OK;
+  if (pieces) { pieces->v = nullptr; pieces->n = 0; }
+  MK_INFL_HIP(h, hipSetDevice(h->device));
+  mk_gun_run R;
+  R.S = h->stream;
+  mk_gun_result res;
+  std::vector<mk_gunzip_piece> tab;
+  uint64_t done = 0;
+  bool fits = true;
+  auto read = [&](uint64_t off, uint64_t n, uint8_t *dst) -> int { memcpy(dst, comp + off, n); return MK_OK; };
+  auto sink = [&](uint8_t *d_text, uint64_t n, bool) -> int {
+    if (done + n > cap) fits = false;
+    else if (n && hipMemcpyAsync(text_out + done, d_text + MK_FQ_CARRY, n, hipMemcpyDeviceToHost, R.S) != hipSuccess) return MK_ERR_HIP;
+    done += n;
+    return MK_OK;
+  };
+  const int rc = mk_gun_stream(R, comp_bytes, *info, opts, read, sink, &tab, res);
+  if (rc) return mk_infl_fail(h, rc, "mk_inflate_stream: %s", R.err[0] ? R.err : "copying the text back failed");
+  *text_len = res.text_len;
+  *status = res.status;
+  h->inflate_ms = res.find_ms + res.decode_ms + res.resolve_ms;
+  if (pieces && !tab.empty()) {
+    pieces->v = (mk_gunzip_piece *)malloc(tab.size() * sizeof(mk_gunzip_piece));
+    if (!pieces->v) return MK_ERR_NOMEM;
+    memcpy(pieces->v, tab.data(), tab.size() * sizeof(mk_gunzip_piece));
+    pieces->n = tab.size();
+  }
+  if (!fits && !res.status) return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_stream: the text has %llu bytes, cap is %llu", (unsigned long long)res.text_len, (unsigned long long)cap);
+  return MK_OK;
+}
+
+extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, uint64_t first_ordinal, mk_gunzip_stats *st) {
+  if (!e || fd < 0) return MK_ERR_ARG;
+  mk_gunzip_stats stats;
+  memset(&stats, 0, sizeof stats);
+  stats.bad_piece = -1;
+  if (st) *st = stats;
+  const double t_begin = mk_now_s();
+  mk_gzip_info info;
+  int rc = mk_gzip_scan_stream(fd, nullptr, size, &info);
+  if (rc) return rc;
+  if (!info.is_single) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "not a single-member gzip file"); return MK_ERR_ARG; }
+  void *sp = nullptr;
+  int device = 0;
+  rc = mk_engine_get_stream(e, &sp, &device);
+  if (rc) return rc;
+  struct frame_bufs { /* the framing's own buffers */
+    uint8_t *d_rows = nullptr, *d_carry = nullptr;
+    uint32_t *d_tile_cnt = nullptr, *d_tile_last = nullptr;
+    mk_fq_res *d_res = nullptr, *h_res = nullptr;
+    uint64_t rows_cap = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~frame_bufs() {
+      (void)hipFree(d_rows); (void)hipFree(d_carry); (void)hipFree(d_tile_cnt); (void)hipFree(d_tile_last); (void)hipFree(d_res);
+      if (h_res) (void)hipHostFree(h_res);
+      for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    }
+  } F;
+  mk_gun_run R;
+  R.S = (hipStream_t)sp;
+  hipStream_t S = R.S;
+  MK_GUN_HIP(hipSetDevice(device));
+  const uint32_t max_tiles = mk_fq_ntiles((uint32_t)(MK_FQ_CARRY + MK_GUN_SLICE));
+  MK_GUN_HIP(mk_dev_alloc(&F.d_carry, (size_t)MK_FQ_CARRY));
+  MK_GUN_HIP(mk_dev_alloc(&F.d_tile_cnt, (size_t)max_tiles * sizeof(uint32_t)));
+  MK_GUN_HIP(mk_dev_alloc(&F.d_tile_last, (size_t)max_tiles * sizeof(uint32_t)));
+  MK_GUN_HIP(mk_dev_alloc(&F.d_res, sizeof(mk_fq_res)));
+  MK_GUN_HIP(mk_pin_alloc(&F.h_res, sizeof(mk_fq_res), hipHostMallocDefault));
+  for (int k = 0; k < 2; k++) MK_GUN_HIP(hipEventCreate(&F.ev[k]));
+
+  uint32_t carry = 0; /* bytes behind the last complete record, kept in d_carry between batches */
+  uint64_t ordinal = first_ordinal;
+  bool long_line = false;
+  auto read = [&](uint64_t off, uint64_t n, uint8_t *dst) -> int {
+    for (uint64_t got = 0; got < n;) {
+      const ssize_t r = pread(fd, dst + got, n - got, (off_t)(off + got));
+      if (r <= 0) return MK_ERR_IO;
+      got += (uint64_t)r;
+    }
+    return MK_OK;
+  };
+  auto sink = [&](uint8_t *d_text, uint64_t n, bool final_batch) -> int {
+    if (n == 0 && !final_batch) return MK_OK;
+    { /* rows of one slice at most (a row is a line of the text, padded) */
+      const uint64_t need = std::max<uint64_t>(std::min<uint64_t>(n, MK_GUN_SLICE) + MK_FQ_CARRY, (uint64_t)8 << 20) + 4096u;
+      if (need > F.rows_cap) {
+        MK_GUN_HIP(hipStreamSynchronize(S));
+        (void)hipFree(F.d_rows);
+        F.d_rows = nullptr; F.rows_cap = 0;
+        MK_GUN_HIP(mk_dev_alloc(&F.d_rows, need));
+        F.rows_cap = need;
+      }
+    }
+    if (carry) {
+      hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)F.d_carry, 0u, d_text, MK_FQ_CARRY - carry, carry);
+      MK_GUN_HIP(hipGetLastError());
+    }
+    uint64_t off = 0;
+    do {
+      const uint32_t sl = (uint32_t)std::min<uint64_t>(MK_GUN_SLICE, n - off);
+      const int final = final_batch && off + sl == n;
+      uint8_t *base = d_text + off;
+      const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + sl, nn = e1 - t0;
+      MK_GUN_HIP(hipEventRecord(F.ev[0], S));
+      MK_GUN_HIP(mk_launch_frame_count(S, base, t0, e1, final, F.d_tile_cnt, F.d_tile_last, nullptr, 0, F.d_res));
+      MK_GUN_HIP(hipEventRecord(F.ev[1], S));
+      MK_GUN_HIP(hipMemcpyAsync(F.h_res, F.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
+      MK_GUN_HIP(hipStreamSynchronize(S));
+      const mk_fq_res r = *F.h_res;
+      float ms = 0.f;
+      MK_GUN_HIP(hipEventElapsedTime(&ms, F.ev[0], F.ev[1]));
+      stats.frame_ms += ms;
+      if (r.maxline >= MK_FQ_LINE_MAX || (!final && nn - r.consumed > MK_FQ_CARRY)) { long_line = true; return MK_ERR_FORMAT; }
+      const uint32_t stride = mk_fq_stride(r.maxseq), per = (uint32_t)(F.rows_cap / stride);
+      for (uint32_t r0 = 0; r0 < r.nrec; r0 += per) {
+        const uint32_t r1 = r.nrec - r0 < per ? r.nrec : r0 + per;
+        MK_GUN_HIP(mk_launch_frame_rows(S, base, t0, e1, F.d_tile_cnt, r0, r1, stride, F.d_rows));
+        const int prc = mk_sketch_push_reads_device(e, F.d_rows, stride, r1 - r0, ordinal);
+        if (prc) { snprintf(R.err, sizeof R.err, "%s", mk_last_error(e)); return prc; }
+        ordinal += r1 - r0;
+      }
+      stats.rows += r.nrec;
+      carry = nn - r.consumed;
+      off += sl;
+      if (off >= n && carry) { /* behind the batch's last slice: what is left waits for the next batch's text */
+        hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)base, t0 + r.consumed, F.d_carry, 0u, carry);
+        MK_GUN_HIP(hipGetLastError());
+      }
+    } while (off < n);
+    return MK_OK;
+  };
+  mk_gun_result res;
+  rc = mk_gun_stream(R, size, info, opts, read, sink, nullptr, res);
+  (void)hipStreamSynchronize(S);
+  stats.pieces = res.npieces; stats.batches = res.nbatches; stats.comp_bytes = size; stats.text_bytes = res.text_len;
+  stats.find_ms = res.find_ms; stats.decode_ms = res.decode_ms; stats.resolve_ms = res.resolve_ms; stats.t_read_s = res.t_read_s;
+  stats.bad_piece = res.bad_piece; stats.bad_status = res.status;
+  stats.t_total_s = mk_now_s() - t_begin;
+  if (st) *st = stats;
+  if (rc == MK_ERR_FORMAT && long_line) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "a FASTQ line of 4095 characters or more"); return rc; }
+  if (rc) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", R.err); return rc; }
+  if (res.status) {
+    snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "gzip stream, piece %lld: %s", (long long)res.bad_piece, mk_inflate_status_text(res.status));
+    return MK_ERR_FORMAT;
+  }
+  return MK_OK;
+}

@@ -38,6 +38,8 @@
  *                        how long it is (8 bytes a record); the rows kernel masks while it copies.  The first record of a file that
  *                        holds no complete one is walked all the same (iseq2comem.c:343-349): one wave does that serially.  No
  *                        windows: a line of 4095+ characters is refused, the caller takes the host framer for such a file.
+ * mk_gunzip.hip.h (included last): ONE gzip member of any size by many waves -- block-start finder, decode to 16-bit symbols with
+ *                        markers, window chain, resolve -- around this file's bit reader, table builder and CRC kernels.
  * Bound of each kernel: DESIGN.md 4.10, 4.12.
  */
 #include <hip/hip_runtime.h>
@@ -100,8 +102,10 @@ struct mk_infl_lds { /* one wave's */
   uint32_t mat[32];
 };
 
-/* the compressed stream of one member, in coordinates relative to its payload's address rounded down to 16 bytes */
-struct mk_bits {
+/* the compressed stream of one member, in coordinates relative to its payload's address rounded down to 16 bytes.  ZERO_TAIL: the
+ * bytes behind `end` read as zeros whatever lies there (mk_gunzip.hip.h: a status then depends on the stream alone) */
+template <bool ZERO_TAIL>
+struct mk_bits_t {
   const uint8_t *base; /* 16-byte aligned */
   uint32_t *win;
   uint32_t end;        /* first byte behind the payload */
@@ -113,6 +117,13 @@ struct mk_bits {
     const uint32_t a = win_base + 16u * lane;
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (a < end) v = *(const uint4 *)(base + a); /* (a 16-byte piece that starts inside the payload: inside the staging buffer, which ends in slack) */
+    if (ZERO_TAIL && a < end && end - a < 16u) {
+      const uint32_t n = end - a; /* bytes to keep */
+      v.x &= n >= 4u ? ~0u : (1u << (8u * n)) - 1u;
+      v.y &= n >= 8u ? ~0u : n > 4u ? (1u << (8u * (n - 4u))) - 1u : 0u;
+      v.z &= n >= 12u ? ~0u : n > 8u ? (1u << (8u * (n - 8u))) - 1u : 0u;
+      v.w &= n > 12u ? (1u << (8u * (n - 12u))) - 1u : 0u;
+    }
     mk_lds_fence();
     ((uint4 *)win)[lane] = v;
     mk_lds_fence();
@@ -145,9 +156,11 @@ struct mk_bits {
   __device__ __forceinline__ uint64_t bitpos() const { return (uint64_t)next * 8u - cnt; }
   __device__ __forceinline__ bool past_end() const { return bitpos() > (uint64_t)end * 8u; }
 };
+typedef mk_bits_t<false> mk_bits;
 
 /* the canonical walk, a bit at a time (codes longer than the look-up table's index, and every code an incomplete set leaves out) */
-__device__ __forceinline__ int mk_decode_slow(mk_bits &b, const uint16_t *cnt, const uint16_t *sym) {
+template <class B>
+__device__ __forceinline__ int mk_decode_slow(B &b, const uint16_t *cnt, const uint16_t *sym) {
   int code = 0, first = 0, index = 0;
   for (uint32_t len = 1; len <= 15u; len++) {
     code |= (int)b.get(1);
@@ -160,7 +173,8 @@ __device__ __forceinline__ int mk_decode_slow(mk_bits &b, const uint16_t *cnt, c
   }
   return -1;
 }
-__device__ __forceinline__ int mk_decode(mk_bits &b, const uint16_t *tab, uint32_t bits, const uint16_t *cnt, const uint16_t *sym) {
+template <class B>
+__device__ __forceinline__ int mk_decode(B &b, const uint16_t *tab, uint32_t bits, const uint16_t *cnt, const uint16_t *sym) {
   const uint32_t e = mk_uni(tab[(uint32_t)b.buf & ((1u << bits) - 1u)]);
   const uint32_t l = e & 15u;
   if (l) { b.buf >>= l; b.cnt -= l; return (int)(e >> 4); }
@@ -1337,3 +1351,5 @@ extern "C" int mk_sketch_push_bgzf_q(mk_engine *e, int fd, size_t size, const mk
 }
 
 extern "C" const char *mk_bgzf_last_error(void) { return mk_bgzf_err; }
+
+#include "mk_gunzip.hip.h"

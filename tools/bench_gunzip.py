@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""tools/bench_gunzip.py -- an ordinary single-member `.fastq.gz` through `metakssd dist -L L3K11.shuf -A`: the opt-in device route
+(`--device-gunzip`: finder, decode to symbols, window chain, resolve, CRC32 and FASTQ framing on the GPU) against
+the default route (the `zcat -fc` pipe; with --parent-cli also a binary built from the parent commit), `zcat -fc` alone and the
+uncompressed file; prints one JSON line.  Built on tools/bench_bgzf.py's plan.
+
+The input is bench.py's read stream (mk_synth_fastq_write_mt, same seed and read length) compressed as ONE gzip member with zlib at
+level 1 and level 6.  Per level the legs run --runs times taking turns, each from process start to the directory on disk; medians
+are reported and the sketch directories must be byte-equal.  Then the span size S is timed at 128 KiB .. 1 MiB on the last level's
+file, and mk_inflate_stream's piece table gives the largest text-to-compressed ratio any piece showed (what R must stay above)."""
+import argparse
+import filecmp
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+import zlib
+from concurrent.futures import ProcessPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+CLI = os.path.join(ROOT, "metakssd_amd", "bin", "metakssd")
+SEED, READ_LEN = 20261002, 150  # bench.py's SEED and READ_LEN
+SPANS = (128 << 10, 256 << 10, 512 << 10, 1 << 20)
+
+
+def compress(args):
+    src, dst, level = args
+    c = zlib.compressobj(level, zlib.DEFLATED, 31)
+    with open(src, "rb") as f, open(dst, "wb") as g:
+        while True:
+            b = f.read(16 << 20)
+            if not b:
+                break
+            g.write(c.compress(b))
+        g.write(c.flush())
+    return os.path.getsize(dst)
+
+
+def run_cli(cli, shuf, out, inp, extra):
+    shutil.rmtree(out, ignore_errors=True)
+    t0 = time.perf_counter()
+    r = subprocess.run([cli, "dist", "-L", shuf, "-A", "-o", out, "--quiet", "--timing"] + extra + [inp], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=3000)
+    dt = time.perf_counter() - t0
+    if r.returncode != 0:
+        raise RuntimeError(r.stderr.decode(errors="replace")[-500:])
+    route = [json.loads(ln) for ln in r.stdout.decode().splitlines() if ln.startswith('{"input"')]
+    return dt, route[0] if route else None
+
+
+def same(a, b):
+    files = sorted(os.listdir(a))
+    return files == sorted(os.listdir(b)) and all(filecmp.cmp(os.path.join(a, f), os.path.join(b, f), shallow=False) for f in files)
+
+
+def med(xs):
+    return round(statistics.median(xs), 4)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=2000000)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--span-runs", type=int, default=3)
+    ap.add_argument("--levels", default="1,6")
+    ap.add_argument("--workdir", default=None)
+    ap.add_argument("--parent-cli", default=None, help="a metakssd binary built from the parent commit: its default route is timed too")
+    ap.add_argument("--rocprof", default=None, help="directory: one more device-route run per level under `rocprofv3 --kernel-trace --stats`")
+    a = ap.parse_args()
+    from golden_cases import make_shuf
+    from metakssd_amd import capi
+    if capi.device_count() < 1:
+        sys.exit("bench_gunzip: no HIP device")
+    tmp = tempfile.mkdtemp(prefix="mkgunzip_", dir=a.workdir or ("/dev/shm" if os.path.isdir("/dev/shm") else None))
+    levels = [int(x) for x in a.levels.split(",")]
+    out = {"what": "`metakssd dist -L L3K11.shuf -A` on %d reads of %d bases as ONE gzip member, median of %d runs from process start to the "
+                   "directory on disk, legs taking turns" % (a.reads, READ_LEN, a.runs), "reads": a.reads, "levels": {}}
+    try:
+        shuf = os.path.join(tmp, "L3K11.shuf")
+        make_shuf("L3K11", shuf)
+        fq = os.path.join(tmp, "reads.fq")
+        assert capi.lib.mk_synth_fastq_write_mt(fq.encode(), SEED, 0, a.reads, READ_LEN, 16) == 0
+        text_bytes, bases = os.path.getsize(fq), a.reads * READ_LEN
+        out["text_bytes"] = text_bytes
+        gzs = {lv: os.path.join(tmp, "reads.l%d.fq.gz" % lv) for lv in levels}
+        with ProcessPoolExecutor(len(levels)) as ex:
+            comps = dict(zip(levels, ex.map(compress, [(fq, gzs[lv], lv) for lv in levels])))
+        d_plain = os.path.join(tmp, "plain")
+        t_plain = statistics.median(run_cli(CLI, shuf, d_plain, fq, [])[0] for _ in range(3))
+        out["plain_fastq"] = {"wall_s": round(t_plain, 4), "gbases_s": round(bases / t_plain / 1e9, 3)}
+        gb = lambda t: round(bases / t / 1e9, 3)
+        for lv in levels:
+            print("bench_gunzip: level %d, %d bytes" % (lv, comps[lv]), file=sys.stderr, flush=True)
+            gz = gzs[lv]
+            dev, zc, par, zo, routes = [], [], [], [], []
+            d_dev, d_zc = os.path.join(tmp, "dev"), os.path.join(tmp, "zc")
+            for _ in range(a.runs):
+                dt, route = run_cli(CLI, shuf, d_dev, gz, ["--device-gunzip"])
+                assert route and route["route"] == "device-gunzip", route
+                dev.append(dt); routes.append(route)
+                dt, route = run_cli(CLI, shuf, d_zc, gz, [])
+                assert route and route["route"] == "zcat" and "fallback" not in route, route
+                zc.append(dt)
+                if a.parent_cli:
+                    par.append(run_cli(a.parent_cli, shuf, os.path.join(tmp, "par"), gz, [])[0])
+                t0 = time.perf_counter()
+                subprocess.run(["zcat", "-fc", "--", gz], stdout=subprocess.DEVNULL, check=True)
+                zo.append(time.perf_counter() - t0)
+            if a.rocprof:
+                os.makedirs(a.rocprof, exist_ok=True)
+                subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", a.rocprof, "-o", "gunzip_l%d" % lv, "--", CLI, "dist", "-L", shuf, "-A", "-o",
+                                os.path.join(tmp, "prof"), "--quiet", "--slow-exit", "--device-gunzip", gz], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+            k = {f: med([r[f] for r in routes]) for f in ("find_ms", "decode_ms", "resolve_ms", "frame_ms", "read_s", "route_total_s")}
+            out["levels"][str(lv)] = {
+                "comp_bytes": comps[lv], "ratio": round(text_bytes / comps[lv], 3), "pieces": routes[0]["pieces"], "batches": routes[0]["batches"],
+                "device_gunzip": {"wall_s": med(dev), "gbases_s": gb(statistics.median(dev)), "runs_s": [round(x, 4) for x in dev]},
+                "zcat_route": {"wall_s": med(zc), "gbases_s": gb(statistics.median(zc)), "runs_s": [round(x, 4) for x in zc]},
+                "parent_zcat_route": {"wall_s": med(par), "gbases_s": gb(statistics.median(par))} if par else None,
+                "zcat_alone": {"wall_s": med(zo), "gbases_s": gb(statistics.median(zo))},
+                "speedup_vs_zcat_route": round(statistics.median(zc) / statistics.median(dev), 2),
+                "speedup_vs_parent": round(statistics.median(par) / statistics.median(dev), 2) if par else None,
+                "kernels_ms": k,
+                "decode_text_gb_s": round(text_bytes / k["decode_ms"] / 1e6, 2),
+                "sketch_dirs_equal": bool(same(d_dev, d_zc)),
+            }
+        # the span size, on the last level's file
+        gz, sweep = gzs[levels[-1]], {}
+        for S in SPANS:
+            print("bench_gunzip: span %d" % S, file=sys.stderr, flush=True)
+            ts, rs = [], []
+            for _ in range(a.span_runs):
+                dt, route = run_cli(CLI, shuf, os.path.join(tmp, "dev"), gz, ["--device-gunzip", "--gunzip-span-bytes", str(S)])
+                assert route and route["route"] == "device-gunzip", route
+                ts.append(dt); rs.append(route)
+            sweep[str(S)] = {"wall_s": med(ts), "pieces": rs[0]["pieces"], "batches": rs[0]["batches"],
+                             "find_ms": med([r["find_ms"] for r in rs]), "decode_ms": med([r["decode_ms"] for r in rs]), "resolve_ms": med([r["resolve_ms"] for r in rs])}
+        out["span_sweep_level_%d" % levels[-1]] = sweep
+        # the largest ratio a piece showed, at the default span
+        worst = {}
+        infl = capi.Inflate(0)
+        for lv in levels:
+            comp = open(gzs[lv], "rb").read()
+            info = capi.gzip_scan_stream(comp)
+            text, st, pieces, n = infl.stream(comp, cap=text_bytes)
+            assert st == 0 and n == text_bytes and zlib.crc32(text) == info["crc32"]
+            ends = [p for p, _ in pieces[1:]] + [8 * info["pay_len"]]
+            worst[str(lv)] = round(max(n / ((e + 7) // 8 - p // 8) for (p, n), e in zip(pieces, ends)), 2)
+            del comp, text
+        infl.close()
+        out["largest_piece_ratio"] = worst
+        out["ok"] = all(v["sketch_dirs_equal"] for v in out["levels"].values())
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    print(json.dumps(out))
+    return 0 if out.get("ok") else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
