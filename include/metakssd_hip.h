@@ -885,6 +885,10 @@ int mk_sketch_batch_gz_status(mk_engine *e, uint32_t *status, uint32_t nfiles);
  *   mk_sketch_push_gzip   the same bound to an engine: the text is framed and scanned like mk_sketch_push_bgzf's */
 #define MK_INFL_MISSED 9    /* a piece decoded past the start of the next one: the finder's candidate was no block start */
 #define MK_INFL_CAPACITY 10 /* a piece gave more than R times the compressed bytes it covers */
+/* eleven: (MK_GUNZIP_MEMBERS) behind a member's trailer and in front of the payload's end the bytes are not a gzip header with at
+ * least one payload byte behind it: a wrong magic, CM != 8, reserved FLG bits, optional fields that run past the payload, or fewer
+ * than 8 + 10 + 1 bytes left (zero padding, garbage) */
+#define MK_INFL_BAD_MEMBER (MK_INFL_CAPACITY + 1)
 /* mk_gzip_scan's rule with two differences: ISIZE, which is only the text's length mod 2^32, has no upper limit and may be 0, and
  * the payload may be of any length.  A BGZF file and a concatenation of members pass, as they do there: the caller asks
  * mk_bgzf_scan first, and the decode says MK_INFL_TRAILING.  Host code only. */
@@ -894,10 +898,20 @@ typedef struct mk_gunzip_opts {
   uint32_t ratio;       /* R: symbols a piece may give per compressed byte it covers; 0 = 16 */
   uint32_t batch_spans; /* spans whose pieces are decoded, resolved and framed together; 0 = as many as keep R * S * spans within
                          * 2 GiB of text (1024 with the defaults), which is also the most */
-  uint32_t reserved;
+  uint32_t flags;       /* MK_GUNZIP_*; 0 = one member, as ever */
 } mk_gunzip_opts;
+/* The file may be a CONCATENATION of members (`cat a.gz b.gz`, `gzip >>`): behind a final block that ends in front of the payload's
+ * end the decode reads the member's trailer, walks the next header (FEXTRA, FNAME, FCOMMENT, FHCRC as FLG says; FHCRC is not
+ * verified) and goes on; every member's length mod 2^32 and CRC32 are held against its own trailer, and the first member in stream
+ * order that fails gives MK_INFL_OUTPUT_LEN or MK_INFL_CRC -- behind any status a piece gave.  Distances are held against the
+ * member's start wherever a piece has seen that start.  The finder takes a member start whose first block is a dynamic one for a
+ * piece start too.  Without the flag a second member is MK_INFL_TRAILING. */
+#define MK_GUNZIP_MEMBERS 1u
+/* bit 63 of mk_gunzip_piece.start_bit (MK_GUNZIP_MEMBERS only): the piece starts at a member's header; the lower bits are 8 * the
+ * header's first byte, in payload coordinates */
+#define MK_GUNZIP_PIECE_MEMBER ((uint64_t)1 << 63)
 typedef struct mk_gunzip_piece {
-  uint64_t start_bit; /* in the payload */
+  uint64_t start_bit; /* in the payload; bit 63: MK_GUNZIP_PIECE_MEMBER */
   uint64_t text_len;  /* bytes of text it gave */
 } mk_gunzip_piece;
 typedef struct mk_gunzip_pieces {
@@ -914,6 +928,11 @@ void mk_gunzip_pieces_free(mk_gunzip_pieces *p);
  * The call returns MK_OK whatever the status is. */
 int mk_inflate_stream(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_gzip_info *info, const mk_gunzip_opts *opts,
                       uint8_t *text_out, size_t cap, uint64_t *text_len, int32_t *status, mk_gunzip_pieces *pieces);
+/* members whose end the last mk_inflate_stream on h met and checked (with MK_INFL_OK: the members of the file; 1 without the flag) */
+int mk_inflate_stream_members(mk_inflate *h, uint64_t *members);
+/* mk_inflate_status_text with a line for MK_INFL_BAD_MEMBER, the status only this route with MK_GUNZIP_MEMBERS gives (the older
+ * function keeps answering "unknown status" above MK_INFL_CAPACITY, as its callers and tests know it) */
+const char *mk_gunzip_status_text(int status);
 typedef struct mk_gunzip_stats {
   uint64_t pieces, batches, comp_bytes, text_bytes, rows;
   double find_ms, decode_ms, resolve_ms; /* device time of the finder, the decode to symbols, window chain + resolve + CRC */
@@ -921,7 +940,7 @@ typedef struct mk_gunzip_stats {
   double t_read_s, t_total_s;            /* host: reading the file into pinned staging, the whole call */
   int64_t bad_piece;   /* MK_ERR_FORMAT from the decode: the piece's index in the stream (-1: the trailer check, or a long line) */
   int32_t bad_status;  /* ... and the MK_INFL_* status (0: a line of 4095+ characters) */
-  int32_t reserved;
+  uint32_t members;    /* members whose end was met and checked */
 } mk_gunzip_stats;
 /* The first `size` bytes behind fd, a file mk_gzip_scan_stream accepts (MK_ERR_ARG otherwise), go into the sketch begun on e with
  * mk_sketch_begin (the -A reader): batch after batch the text is made as in mk_inflate_stream and framed in slices of at most

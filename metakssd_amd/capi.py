@@ -134,7 +134,7 @@ class BgzfStatsC(C.Structure):
 
 
 class GunzipOptsC(C.Structure):
-    _fields_ = [("span_bytes", C.c_uint32), ("ratio", C.c_uint32), ("batch_spans", C.c_uint32), ("reserved", C.c_uint32)]
+    _fields_ = [("span_bytes", C.c_uint32), ("ratio", C.c_uint32), ("batch_spans", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class GunzipPieceC(C.Structure):
@@ -148,7 +148,7 @@ class GunzipPiecesC(C.Structure):
 class GunzipStatsC(C.Structure):
     _fields_ = [("pieces", C.c_uint64), ("batches", C.c_uint64), ("comp_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("rows", C.c_uint64),
                 ("find_ms", C.c_double), ("decode_ms", C.c_double), ("resolve_ms", C.c_double), ("frame_ms", C.c_double),
-                ("t_read_s", C.c_double), ("t_total_s", C.c_double), ("bad_piece", C.c_int64), ("bad_status", C.c_int32), ("reserved", C.c_int32)]
+                ("t_read_s", C.c_double), ("t_total_s", C.c_double), ("bad_piece", C.c_int64), ("bad_status", C.c_int32), ("members", C.c_uint32)]
 
 
 def _load():
@@ -191,6 +191,7 @@ def _load():
         "mk_gzip_scan_stream": [C.c_int, vp, C.c_size_t, C.POINTER(GzipInfoC)],
         "mk_inflate_stream": [vp, vp, C.c_size_t, C.POINTER(GzipInfoC), C.POINTER(GunzipOptsC), vp, C.c_size_t, C.POINTER(u64), C.POINTER(i32),
                               C.POINTER(GunzipPiecesC)],
+        "mk_inflate_stream_members": [vp, C.POINTER(u64)],
         "mk_sketch_push_gzip": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), u64, C.POINTER(GunzipStatsC)],
         "mk_inflate_members": [vp, vp, C.c_size_t, C.POINTER(GzMemberC), u32, vp, C.c_size_t, C.POINTER(GzMemberResultC)],
         "mk_sketch_finish": [vp, C.POINTER(ResultC)],
@@ -310,6 +311,8 @@ def _load():
     lib.mk_inflate_last_error.restype = C.c_char_p
     lib.mk_inflate_status_text.argtypes = [C.c_int]
     lib.mk_inflate_status_text.restype = C.c_char_p
+    lib.mk_gunzip_status_text.argtypes = [C.c_int]
+    lib.mk_gunzip_status_text.restype = C.c_char_p
     lib.mk_bgzf_last_error.argtypes = []
     lib.mk_bgzf_last_error.restype = C.c_char_p
     lib.mk_bgzf_free.argtypes = [C.POINTER(BgzfBlockC)]
@@ -589,10 +592,10 @@ class Engine:
             raise err
         return st
 
-    def push_gzip(self, path, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0):
+    def push_gzip(self, path, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0, members=False):
         """a single-member gzip FASTQ file into the sketch in progress (mk_sketch_push_gzip) -> GunzipStatsC; an inflate status or
         a long line raises MkError(MK_ERR_FORMAT) with the statistics in .stats: the sketch is then to be begun anew"""
-        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, 0), GunzipStatsC()
+        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), GunzipStatsC()
         fd = os.open(path, os.O_RDONLY)
         try:
             rc = lib.mk_sketch_push_gzip(self.h, fd, os.fstat(fd).st_size, C.byref(o), first_ordinal, C.byref(st))
@@ -1236,7 +1239,9 @@ MK_BYREAD_MAX_PUSH = 8 << 20
 
 
 MK_INFL_OK, MK_INFL_BAD_BLOCK, MK_INFL_BAD_LENGTHS, MK_INFL_BAD_CODE, MK_INFL_BAD_DISTANCE, MK_INFL_INPUT, MK_INFL_OUTPUT_LEN, MK_INFL_CRC = range(8)
-MK_INFL_TRAILING, MK_INFL_MISSED, MK_INFL_CAPACITY = 8, 9, 10
+MK_INFL_TRAILING, MK_INFL_MISSED, MK_INFL_CAPACITY, MK_INFL_BAD_MEMBER = 8, 9, 10, 11
+MK_GUNZIP_MEMBERS = 1
+MK_GUNZIP_PIECE_MEMBER = 1 << 63
 MK_CRC_SLICE = 16384
 BGZF_FIELDS = ("in_off", "out_off", "in_len", "pay_off", "pay_len", "crc32", "isize")
 
@@ -1419,17 +1424,19 @@ class Inflate:
         self._check(lib.mk_inflate_members(self.h, b.ctypes.data if len(b) else None, len(b), arr, n, out.ctypes.data, end, res))
         return out[:end].tobytes(), [(int(r.status), int(r.consumed), int(r.pos), int(r.crc32)) for r in res[:n]]
 
-    def stream(self, comp, span_bytes=0, ratio=0, batch_spans=0, cap=None, guard=64):
+    def stream(self, comp, span_bytes=0, ratio=0, batch_spans=0, cap=None, guard=64, members=False):
         """mk_inflate_stream over a whole gzip file (bytes) -> (text or None, MK_INFL_* status, [(start bit, text length) per piece],
         text length).  The text buffer has cap bytes (default: ISIZE, which is the text's length for texts below 4 GiB) between two
-        guards of `guard` bytes, which must come back untouched."""
+        guards of `guard` bytes, which must come back untouched.  members: MK_GUNZIP_MEMBERS, the file may be a concatenation of
+        members; a piece is then (start bit, kind, text length) with kind 1 where it starts at a member's header, and the members
+        whose end was met come as a fifth value.  cap must then be given for a text that is not ISIZE bytes long."""
         info = gzip_scan_stream(comp, raw=True)
         if info is None:
             raise MkError(MK_ERR_ARG, "not a single-member gzip file")
         b = np.frombuffer(bytes(comp), dtype=np.uint8)
         cap = int(info.isize) if cap is None else cap
         buf = np.full(cap + 2 * guard, 0xC3, dtype=np.uint8)
-        o, n, st, pieces = GunzipOptsC(span_bytes, ratio, batch_spans, 0), C.c_uint64(0), C.c_int32(-1), GunzipPiecesC()
+        o, n, st, pieces = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), C.c_uint64(0), C.c_int32(-1), GunzipPiecesC()
         rc = lib.mk_inflate_stream(self.h, b.ctypes.data, len(b), C.byref(info), C.byref(o), buf.ctypes.data + guard, cap, C.byref(n),
                                    C.byref(st), C.byref(pieces))
         table = [(int(pieces.v[i].start_bit), int(pieces.v[i].text_len)) for i in range(pieces.n)]
@@ -1437,6 +1444,11 @@ class Inflate:
         self._check(rc)
         assert (buf[:guard] == 0xC3).all() and (buf[guard + cap:] == 0xC3).all(), "a write outside the text buffer"
         text = buf[guard:guard + n.value].tobytes() if st.value == 0 else None
+        if members:
+            table = [(s & ~MK_GUNZIP_PIECE_MEMBER, s >> 63, t) for s, t in table]
+            nm = C.c_uint64(0)
+            self._check(lib.mk_inflate_stream_members(self.h, C.byref(nm)))
+            return text, st.value, table, n.value, nm.value
         return text, st.value, table, n.value
 
     def frame(self, text, final=True):

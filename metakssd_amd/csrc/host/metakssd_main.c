@@ -702,18 +702,21 @@ static int sketch_fastq_gunzip(ctx_t *c, const char *path) {
     if (frc != MK_OK && frc != MK_ERR_CROWDED) die("mk_sketch_finish failed (%d): %s", frc, mk_last_error(e));
     if (frc == MK_OK) mk_result_release(e, &dropped);
     c->begun = 0;
-    g_gz_fallback = gs.bad_status ? mk_inflate_status_text(gs.bad_status) : "long line";
+    g_gz_fallback = gs.bad_status ? mk_gunzip_status_text(gs.bad_status) : "long line";
     return 0;
   }
   if (rc != MK_OK) die("mk_sketch_push_gzip failed (%d): %s", rc, mk_bgzf_last_error());
   c->next_ordinal += gs.rows;
   c->nrows_total += gs.rows;
   c->t_last_push = now_s() - g_t0;
-  if (g_timing)
+  if (g_timing) {
+    char members[48] = ""; /* --gunzip-members: how many the file had */
+    if (g_gunzip_opts.flags & MK_GUNZIP_MEMBERS) snprintf(members, sizeof members, ", \"members\": %u", gs.members);
     printf("{\"input\": \"%s\", \"route\": \"device-gunzip\", \"pieces\": %llu, \"batches\": %llu, \"comp_bytes\": %llu, \"text_bytes\": %llu, \"rows\": %llu, "
-           "\"find_ms\": %.3f, \"decode_ms\": %.3f, \"resolve_ms\": %.3f, \"frame_ms\": %.3f, \"read_s\": %.4f, \"route_total_s\": %.4f}\n",
+           "\"find_ms\": %.3f, \"decode_ms\": %.3f, \"resolve_ms\": %.3f, \"frame_ms\": %.3f, \"read_s\": %.4f, \"route_total_s\": %.4f%s}\n",
            path, (unsigned long long)gs.pieces, (unsigned long long)gs.batches, (unsigned long long)gs.comp_bytes, (unsigned long long)gs.text_bytes,
-           (unsigned long long)gs.rows, gs.find_ms, gs.decode_ms, gs.resolve_ms, gs.frame_ms, gs.t_read_s, gs.t_total_s);
+           (unsigned long long)gs.rows, gs.find_ms, gs.decode_ms, gs.resolve_ms, gs.frame_ms, gs.t_read_s, gs.t_total_s, members);
+  }
   return 1;
 }
 
@@ -2869,6 +2872,7 @@ int main(int argc, char **argv) {
      * the -n / -Q reader (4.12); the -A reader's BGZF route needs no switch.  The later of the two switches holds. */
     else if (!strcmp(argv[i], "--device-inflate")) { g_no_device_inflate = 0; g_gz_batches = 1; g_device_inflate_q = 1; }
     else if (!strcmp(argv[i], "--device-gunzip")) g_device_gunzip = 1; /* dist -A: a single-member .gz FASTQ inflated on the device */
+    else if (!strcmp(argv[i], "--gunzip-members")) g_gunzip_opts.flags |= MK_GUNZIP_MEMBERS; /* ... and a concatenation of members */
     else if (!strcmp(argv[i], "--gunzip-span-bytes") && i + 1 < argc) g_gunzip_opts.span_bytes = (uint32_t)atoll(argv[++i]);
     else if (!strcmp(argv[i], "--gunzip-ratio") && i + 1 < argc) g_gunzip_opts.ratio = (uint32_t)atoll(argv[++i]);
     else if (!strcmp(argv[i], "--gunzip-batch-spans") && i + 1 < argc) g_gunzip_opts.batch_spans = (uint32_t)atoll(argv[++i]);

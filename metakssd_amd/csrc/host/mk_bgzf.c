@@ -101,3 +101,8 @@ const char *mk_inflate_status_text(int status) {
     default: return "unknown status";
   }
 }
+
+const char *mk_gunzip_status_text(int status) {
+  if (status == MK_INFL_BAD_MEMBER) return "no gzip member behind a member's trailer";
+  return mk_inflate_status_text(status);
+}

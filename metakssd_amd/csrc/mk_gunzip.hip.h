@@ -18,7 +18,22 @@
  * The text's CRC32 is mk_crc32_files_kernel's and the combine kernel's over segments of at most 1 GiB, carried from batch to batch
  * on the host.  Safety: the finder and the decode load inside the uploaded payload and the zeroed slack behind it, a piece stores
  * inside its cap symbols, the chain inside its windows, the resolve inside the sum of the lengths the decode reported; every loop
- * consumes input bits or produces output symbols and is bounded by the two sizes.  Bound of each kernel: DESIGN.md 4.14. */
+ * consumes input bits or produces output symbols and is bounded by the two sizes.  Bound of each kernel: DESIGN.md 4.14.
+ *
+ * MK_GUNZIP_MEMBERS: the payload may hold further members, each behind the trailer of the one in front.  The
+ * <true> instances of finder and decode are for it; the <false> ones are the kernels described above, unchanged.
+ *   finder     a second rule at byte-aligned lanes: a gzip header of at most MK_GUN_HDR_MAX bytes and behind it a dynamic block
+ *              header, final or not, that passes the block rule's validation.  The kind travels in bit 63 of cand[].
+ *   decode     behind a final block in front of the payload's end: the trailer into a member record {symbols so far, CRC32,
+ *              ISIZE}, a stop where the next piece starts at the header behind it, else the header walk (MK_INFL_BAD_MEMBER when
+ *              there is none) and on.  Distances are held against the member's start wherever the piece has seen it.
+ *   check      mk_gun_members_kernel turns the records into text positions of the batch; the CRC table has a segment per member
+ *              range, and the host holds every member's length and CRC32 against its own trailer.
+ * Safety: trailer and header bytes are loaded below pay_len only, the FNAME and FCOMMENT walks compare every address with the
+ * payload's end before the load; a piece's records stay inside its mem_cap slots, the count tested before every store (a member
+ * takes 20 compressed bytes, the slots are counted from that, so the test never fails); every loop consumes input -- a boundary 18
+ * bytes, a turn of the name walk 64; MK_POISON covers the record buffers, of which only entries below the count are read; plain
+ * C++ and vector stores only. */
 
 #include <algorithm>
 
@@ -41,9 +56,62 @@ struct mk_gun_piece { /* the device's table, one entry a piece of the batch */
   uint32_t first;    /* the stream's first piece: nothing lies in front of it */
   uint32_t status, len; /* left by the decode */
   uint64_t stop;     /* the bit the decode stopped at */
+  /* MK_GUNZIP_MEMBERS (zeros without it) */
+  uint32_t kind;     /* MK_GUN_K_* */
+  uint32_t mem_cap;  /* member records it may write: (bytes covered) / 20 + 2 */
+  uint64_t mem_off;  /* its records in the batch's record buffer */
+  uint32_t nmem;     /* left by the decode: members that ended in the piece */
+  uint32_t rec_off;  /* the host's prefix sum over nmem: its records in the batch's dense list */
+};
+#define MK_GUN_K_MEMBER 1u      /* the piece starts at a member's header */
+#define MK_GUN_K_NEXT_MEMBER 2u /* the next piece does */
+#define MK_GUN_HDR_MAX 4096u    /* the longest member header the finder walks; the decode walks any */
+
+struct mk_gun_member { /* a member's end as the decode met it */
+  uint32_t at;       /* decode: symbols of the piece in front of the end; dense list: text bytes of the batch in front of it */
+  uint32_t crc32, isize; /* its trailer */
+  uint32_t pad;
 };
 
 __device__ __forceinline__ uint64_t mk_uni64(uint64_t v) { return (uint64_t)mk_uni((uint32_t)(v >> 32)) << 32 | mk_uni((uint32_t)v); }
+
+/* The first payload byte behind the member header at payload byte q, by the whole wave and the same in every lane.  0: no header
+ * there with a payload byte behind it -- a wrong magic, CM != 8, reserved FLG bits, a field that runs past the payload -- or one
+ * longer than `most` bytes.  FHCRC is skipped, not verified.  Loads: payload bytes below pay_len; each turn of the FNAME / FCOMMENT
+ * walk takes 64 of them. */
+__device__ uint64_t mk_gun_header_end(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len, uint64_t q, uint64_t most, uint32_t lane) {
+  if (q >= pay_len || pay_len - q < 10u) return 0;
+  const uint8_t *p = comp + shift;
+  const uint32_t w = mk_uni((uint32_t)p[q] | (uint32_t)p[q + 1u] << 8 | (uint32_t)p[q + 2u] << 16 | (uint32_t)p[q + 3u] << 24);
+  if ((w & 0xe0ffffffu) != 0x00088b1fu) return 0;
+  const uint32_t flg = w >> 24;
+  const uint64_t lim = pay_len - q < most ? pay_len : q + most; /* the header ends at or in front of this byte */
+  uint64_t at = q + 10u;
+  if (at > lim) return 0;
+  if (flg & 4u) { /* FEXTRA */
+    if (lim - at < 2u) return 0;
+    const uint32_t xlen = mk_uni((uint32_t)p[at] | (uint32_t)p[at + 1u] << 8);
+    at += 2u;
+    if (lim - at < xlen) return 0;
+    at += xlen;
+  }
+  for (uint32_t bit = 8u; bit <= 16u; bit <<= 1) { /* FNAME, FCOMMENT: zero-terminated */
+    if (!(flg & bit)) continue;
+    bool hit = false;
+    while (at < lim) {
+      const uint64_t a = at + lane;
+      const uint64_t m = __ballot(a < lim && p[a] == 0);
+      if (m) { at += (uint64_t)__builtin_ctzll(m) + 1u; hit = true; break; }
+      at += 64u;
+    }
+    if (!hit) return 0;
+  }
+  if (flg & 2u) { /* FHCRC */
+    if (lim - at < 2u) return 0;
+    at += 2u;
+  }
+  return at < pay_len ? at : 0;
+}
 
 /* the dynamic block header behind BTYPE (b refilled): HLIT, HDIST, HCLEN, the code length code, the lengths into L.lens[0, nl + nd)
  * -> MK_INFL_*, the same in every lane */
@@ -103,7 +171,11 @@ __device__ __forceinline__ int64_t mk_gun_seek(mk_zbits &b, const uint8_t *comp,
   return 8 * ((int64_t)base_off - (int64_t)shift);
 }
 
-/* cand[i]: the candidate of span span0 + i (span0 >= 1), MK_GUN_NONE when the span has none */
+/* cand[i]: the candidate of span span0 + i (span0 >= 1), MK_GUN_NONE when the span has none.  MEMBERS: the lowest position of
+ * either kind -- a block start as ever, or 8 * (a byte q at which a member header of at most MK_GUN_HDR_MAX bytes stands and, at the
+ * first bit behind it, a dynamic block header, final or not, that passes the same validation), with MK_GUNZIP_PIECE_MEMBER set.
+ * The two never meet at one bit: 0x1f has BFINAL set. */
+template <bool MEMBERS>
 __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_find_kernel(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len, uint32_t S,
                                                                           uint64_t span0, uint32_t nspans, uint64_t *cand) {
   __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
@@ -117,7 +189,7 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_find_kernel(const u
   uint64_t found = MK_GUN_NONE;
   for (uint64_t p0 = lo; p0 < hi && found == MK_GUN_NONE; p0 += 64u) {
     const uint64_t p = p0 + lane;
-    bool ok = false;
+    bool ok = false, okm = false;
     if (p < hi) { /* 128 bits from bit p on: four aligned words, inside the payload, its trailer and the slack */
       const uint64_t q = p + 8u * shift;
       const uint64_t w = q >> 5;
@@ -135,29 +207,45 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_find_kernel(const u
         }
         ok = kraft == 128u;
       }
+      if (MEMBERS) okm = ((uint32_t)p & 7u) == 0u && (h & 0xe0ffffffu) == 0x00088b1fu && p + 32u <= nbits;
     }
-    uint64_t m = __ballot(ok);
+    const uint64_t mm = MEMBERS ? __ballot(okm) : 0ull;
+    uint64_t m = __ballot(ok) | mm;
     while (m && found == MK_GUN_NONE) { /* the survivors, lowest bit first, each by the whole wave */
-      const uint64_t cp = p0 + (uint64_t)__builtin_ctzll(m);
+      const uint32_t at = (uint32_t)__builtin_ctzll(m);
+      const uint64_t cp = p0 + (uint64_t)at;
+      const bool member = MEMBERS && ((mm >> at) & 1ull);
       m &= m - 1ull;
+      uint64_t hb = cp; /* where the block header stands */
+      if (member) {
+        const uint64_t he = mk_gun_header_end(comp, shift, pay_len, cp >> 3, MK_GUN_HDR_MAX, lane);
+        if (!he) continue;
+        hb = 8u * he;
+      }
       mk_zbits b;
       b.win = L.win;
       b.lane = lane;
-      mk_gun_seek(b, comp, shift, pay_len, cp);
+      mk_gun_seek(b, comp, shift, pay_len, hb);
       b.refill();
-      b.get(3);
+      if (member) {
+        b.get(1);
+        if (b.get(2) != 2u) continue;
+      } else b.get(3);
       uint32_t nl = 0, nd = 0;
       if (mk_dyn_lengths(b, L, lane, nl, nd) || b.past_end()) continue;
       if (mk_build(L.lens, nl, L.lit_cnt, L.lit_sym, L.lit_tab, MK_INFL_LBITS, false, lane)) continue;
       if (mk_build(L.lens + nl, nd, L.dist_cnt, L.dist_sym, L.dist_tab, MK_INFL_DBITS, true, lane)) continue;
-      found = cp;
+      found = member ? cp | MK_GUNZIP_PIECE_MEMBER : cp;
     }
   }
   if (lane == 0u) cand[i] = found;
 }
 
+/* MEMBERS: behind a final block that ends in front of the payload's end the wave reads the member's trailer into a member record,
+ * stops where the next piece starts at the header behind it, and otherwise walks that header and decodes on (4.15). */
+template <bool MEMBERS>
 __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len,
-                                                                            mk_gun_piece *pieces, uint32_t npieces, uint16_t *syms) {
+                                                                            mk_gun_piece *pieces, uint32_t npieces, uint16_t *syms, mk_gun_member *mems) {
   __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t k = blockIdx.x * MK_INFL_WAVES + wave;
@@ -167,12 +255,23 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const
   const uint32_t cap = mk_uni(pieces[k].cap), back = mk_uni(pieces[k].first) ? 0u : MK_GUN_WINDOW;
   const bool last_piece = end_bit == MK_GUN_NONE;
   uint16_t *out = syms + mk_uni64(pieces[k].sym_off);
+  const uint32_t kind = MEMBERS ? mk_uni(pieces[k].kind) : 0u, mem_cap = MEMBERS ? mk_uni(pieces[k].mem_cap) : 0u;
+  const bool next_member = (kind & MK_GUN_K_NEXT_MEMBER) != 0u;
+  mk_gun_member *rec = MEMBERS ? mems + mk_uni64(pieces[k].mem_off) : nullptr;
+  bool seen = back == 0u || (kind & MK_GUN_K_MEMBER); /* the piece has seen the start of the member it is in ... */
+  uint32_t mstart = 0, nmem = 0;                      /* ... at this symbol */
+  uint32_t st = MK_INFL_OK, pos = 0, nlit = 0, synced = 0, lit = 0;
+  uint64_t from_bit = start, stop_bit = MK_GUN_NONE;
+  if (MEMBERS && (kind & MK_GUN_K_MEMBER)) { /* a member-start piece begins by walking its header */
+    const uint64_t he = mk_gun_header_end(comp, shift, pay_len, start >> 3, ~(uint64_t)0, lane);
+    if (he) from_bit = 8u * he;
+    else st = MK_INFL_BAD_MEMBER;
+  }
   mk_zbits b;
   b.win = L.win;
   b.lane = lane;
-  const int64_t bit0 = mk_gun_seek(b, comp, shift, pay_len, start);
+  int64_t bit0 = mk_gun_seek(b, comp, shift, pay_len, from_bit);
 
-  uint32_t st = MK_INFL_OK, pos = 0, nlit = 0, synced = 0, lit = 0;
   auto flush = [&]() { /* pending literals -> one store (they were counted against cap when they came) */
     if (nlit) {
       if (lane < nlit) out[pos + lane] = (uint16_t)lit;
@@ -180,11 +279,11 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const
       nlit = 0;
     }
   };
-  for (;;) {
+  while (!st) {
     b.refill();
     if (!last_piece) {
       const uint64_t at = (uint64_t)((int64_t)b.bitpos() + bit0);
-      if (at == end_bit) break;
+      if (at == end_bit && !(MEMBERS && next_member)) break;
       if (at > end_bit) { st = MK_INFL_MISSED; break; }
     }
     if (b.past_end()) { st = MK_INFL_INPUT; break; }
@@ -236,7 +335,7 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const
         if (d >= 30) { st = MK_INFL_BAD_DISTANCE; break; }
         const uint32_t dist = (uint32_t)mk_dbase[d] + b.get(mk_dext[d]);
         flush();
-        if (dist > pos + back) { st = MK_INFL_BAD_DISTANCE; break; }
+        if (dist > (MEMBERS && seen ? pos - mstart : pos + back)) { st = MK_INFL_BAD_DISTANCE; break; }
         if (pos + len > cap) { st = MK_INFL_CAPACITY; break; }
         const int32_t from = (int32_t)pos - (int32_t)dist; /* >= -32768; pos < 2^31 */
         if (from + (int32_t)(len < dist ? len : dist) > (int32_t)synced) { mk_store_fence(); synced = pos; } /* the source was written since the last wait */
@@ -249,16 +348,45 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const
       if (st) break;
     }
     if (last) {
-      if (b.past_end()) st = MK_INFL_INPUT;
-      else if (!last_piece || (((uint64_t)((int64_t)b.bitpos() + bit0) + 7u) >> 3) < pay_len) st = MK_INFL_TRAILING;
-      break;
+      if (b.past_end()) { st = MK_INFL_INPUT; break; }
+      if (!MEMBERS) {
+        if (!last_piece || (((uint64_t)((int64_t)b.bitpos() + bit0) + 7u) >> 3) < pay_len) st = MK_INFL_TRAILING;
+        break;
+      }
+      /* the boundary: trailer, member record, the next header.  Every turn takes at least 8 + 10 bytes of input */
+      const uint64_t p = ((uint64_t)((int64_t)b.bitpos() + bit0) + 7u) >> 3; /* <= pay_len: not past the end */
+      if (p == pay_len) { /* the stream ends; the last trailer lies behind the payload */
+        if (!last_piece) st = MK_INFL_MISSED; /* (the next piece's start was not met, and nothing is left) */
+        break;
+      }
+      if (pay_len - p < 8u + 10u + 1u) { st = MK_INFL_BAD_MEMBER; break; }
+      flush();
+      if (nmem >= mem_cap) { st = MK_INFL_CAPACITY; break; } /* (cannot happen: a member takes 20 bytes, the host counted the slots from that) */
+      {
+        const uint8_t *t = comp + shift + p;
+        const uint32_t crc = mk_uni((uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24);
+        const uint32_t isz = mk_uni((uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24);
+        if (lane == 0u) rec[nmem] = mk_gun_member{pos, crc, isz, 0u};
+        nmem++;
+      }
+      const uint64_t q = p + 8u;
+      if (!last_piece) {
+        if (8u * q == end_bit && next_member) { stop_bit = 8u * q; break; }
+        if (8u * q > end_bit) { st = MK_INFL_MISSED; break; }
+      }
+      const uint64_t he = mk_gun_header_end(comp, shift, pay_len, q, ~(uint64_t)0, lane);
+      if (!he) { st = MK_INFL_BAD_MEMBER; break; }
+      bit0 = mk_gun_seek(b, comp, shift, pay_len, 8u * he);
+      seen = true;
+      mstart = pos;
     }
   }
   flush();
   if (lane == 0u) {
     pieces[k].status = st;
     pieces[k].len = pos;
-    pieces[k].stop = (uint64_t)((int64_t)b.bitpos() + bit0);
+    pieces[k].stop = stop_bit != MK_GUN_NONE ? stop_bit : (uint64_t)((int64_t)b.bitpos() + bit0);
+    if (MEMBERS) pieces[k].nmem = nmem;
   }
 }
 
@@ -297,6 +425,17 @@ __global__ void __launch_bounds__(256) mk_gun_resolve_kernel(const mk_gun_piece 
   }
 }
 
+/* blockIdx.x: the piece.  Its member records, symbol positions, become text positions of the batch in the dense list the host reads
+ * (nmem <= mem_cap and rec_off, the prefix sum over nmem, are the host's: it has checked the first and made the second) */
+__global__ void __launch_bounds__(64) mk_gun_members_kernel(const mk_gun_piece *__restrict__ pieces, const mk_gun_member *__restrict__ mems, mk_gun_member *dense) {
+  const mk_gun_piece &P = pieces[blockIdx.x];
+  const uint32_t text0 = (uint32_t)(P.text_off - MK_FQ_CARRY);
+  for (uint32_t i = threadIdx.x; i < P.nmem; i += 64u) {
+    const mk_gun_member m = mems[P.mem_off + i];
+    dense[P.rec_off + i] = mk_gun_member{text0 + m.at, m.crc32, m.isize, 0u};
+  }
+}
+
 /* ---- host ------------------------------------------------------------------------------------------------------------------- */
 static uint32_t mk_crc_mul_host(uint32_t a, uint32_t b) {
   uint32_t p = 0;
@@ -319,7 +458,7 @@ static uint32_t mk_crc_concat(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
 struct mk_gun_result {
   int32_t status = MK_INFL_OK;
   int64_t bad_piece = -1;
-  uint64_t text_len = 0, npieces = 0, nbatches = 0;
+  uint64_t text_len = 0, npieces = 0, nbatches = 0, members = 0;
   double find_ms = 0, decode_ms = 0, resolve_ms = 0, t_read_s = 0;
 };
 
@@ -343,14 +482,16 @@ struct mk_gun_run { /* everything the stream decode allocates, released on every
   uint16_t *d_syms = nullptr;
   uint8_t *d_crctab = nullptr, *h_crctab = nullptr;
   uint32_t *d_crcwork = nullptr, *h_crc = nullptr;
+  mk_gun_member *d_mems = nullptr, *d_dense = nullptr, *h_dense = nullptr;
+  uint64_t mems_cap = 0, dense_cap = 0, hdense_cap = 0;
   uint64_t cand_cap = 0, hcand_cap = 0, pieces_cap = 0, hpieces_cap = 0, syms_cap = 0, win_cap = 0, text_cap = 0, crctab_cap = 0, hcrctab_cap = 0, crcwork_cap = 0, hcrc_cap = 0;
   hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   char err[256] = {0};
   ~mk_gun_run() {
     for (int s = 0; s < 2; s++) { if (h_stage[s]) (void)hipHostFree(h_stage[s]); if (ev_up[s]) (void)hipEventDestroy(ev_up[s]); }
-    void *dev[] = {d_comp, d_win, d_wcarry, d_text, d_cand, d_pieces, d_syms, d_crctab, d_crcwork};
+    void *dev[] = {d_comp, d_win, d_wcarry, d_text, d_cand, d_pieces, d_syms, d_crctab, d_crcwork, d_mems, d_dense};
     for (void *p : dev) (void)hipFree(p);
-    void *pin[] = {h_cand, h_pieces, h_crctab, h_crc};
+    void *pin[] = {h_cand, h_pieces, h_crctab, h_crc, h_dense};
     for (void *p : pin) if (p) (void)hipHostFree(p);
     for (hipEvent_t e : ev_t) if (e) (void)hipEventDestroy(e);
     if (copy) (void)hipStreamDestroy(copy);
@@ -393,6 +534,8 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
   const mk_gun_geom G = mk_gun_geometry(opts);
   const uint64_t pay_len = info.pay_len, f0 = info.pay_off & ~(uint64_t)15u, total = size - f0; /* the device holds file bytes [f0, size) */
   const uint32_t shift = (uint32_t)(info.pay_off - f0), S = G.S;
+  const bool members = opts && (opts->flags & MK_GUNZIP_MEMBERS);
+  const uint64_t ahead = members ? 4096u + MK_GUN_HDR_MAX : 4096u; /* bytes behind a span the finder may read */
   if (!info.is_single || info.pay_off + pay_len + 8u != size || pay_len == 0) { snprintf(R.err, sizeof R.err, "not a single-member gzip file"); return MK_ERR_ARG; }
   const uint64_t NS = (pay_len + S - 1) / S, NB = (NS + G.batch - 1) / G.batch;
   const uint64_t stage_bytes = std::min<uint64_t>(std::max<uint64_t>((uint64_t)G.batch * S, 65536u), (uint64_t)32 << 20);
@@ -430,17 +573,19 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
   };
 
   std::vector<uint64_t> starts(1, 0); /* every piece start known so far, ascending */
+  std::vector<uint8_t> kinds(1, 0);   /* ... and whether it is a member's header */
   uint64_t found = 0;                 /* batches whose candidates are known */
   auto find_batch = [&](uint64_t j) -> int {
     const uint64_t c0 = std::max<uint64_t>(1, j * G.batch), c1 = std::min<uint64_t>(NS, (j + 1) * G.batch);
     if (c1 <= c0) return MK_OK;
     const uint32_t n = (uint32_t)(c1 - c0);
-    int rc = ensure_uploaded(shift + c1 * S + 4096u); /* (a header that starts in the span's last bits ends within 2.3 KB) */
+    int rc = ensure_uploaded(shift + c1 * S + ahead); /* (a block header that starts in the span's last bits ends within 2.3 KB) */
     if (rc) return rc;
     MK_GUN_HIP(mk_gun_grow(&R.d_cand, &R.cand_cap, n));
     MK_GUN_HIP(mk_gun_grow(&R.h_cand, &R.hcand_cap, n, true));
     MK_GUN_HIP(hipEventRecord(R.ev_t[0], R.S));
-    hipLaunchKernelGGL(mk_gun_find_kernel, dim3((n + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, R.S, (const uint8_t *)R.d_comp, shift, pay_len, S, c0, n, R.d_cand);
+    hipLaunchKernelGGL(members ? mk_gun_find_kernel<true> : mk_gun_find_kernel<false>, dim3((n + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, R.S,
+                       (const uint8_t *)R.d_comp, shift, pay_len, S, c0, n, R.d_cand);
     MK_GUN_HIP(hipGetLastError());
     MK_GUN_HIP(hipEventRecord(R.ev_t[1], R.S));
     MK_GUN_HIP(hipMemcpyAsync(R.h_cand, R.d_cand, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, R.S));
@@ -448,12 +593,19 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     float ms = 0.f;
     MK_GUN_HIP(hipEventElapsedTime(&ms, R.ev_t[0], R.ev_t[1]));
     res.find_ms += ms;
-    for (uint32_t i = 0; i < n; i++) if (R.h_cand[i] != MK_GUN_NONE) starts.push_back(R.h_cand[i]);
+    for (uint32_t i = 0; i < n; i++)
+      if (R.h_cand[i] != MK_GUN_NONE) {
+        starts.push_back(R.h_cand[i] & ~MK_GUNZIP_PIECE_MEMBER);
+        kinds.push_back((uint8_t)(R.h_cand[i] >> 63));
+      }
     return MK_OK;
   };
 
   uint64_t idx = 0; /* the first piece that has not been decoded */
-  uint32_t crc = 0;
+  uint32_t crc = 0;      /* of the member in progress: its text up to the last batch's end ... */
+  uint64_t crc_len = 0;  /* ... and that text's length */
+  int32_t member_status = MK_INFL_OK; /* the first member in stream order whose check failed */
+  std::vector<mk_gun_member> segs;    /* the CRC table's segments: at = 1 where one closes a member, whose trailer it then holds */
   for (uint64_t bt = 0; bt < NB && idx < starts.size(); bt++) {
     int rc;
     while (found < std::min<uint64_t>(NB, bt + 1)) { rc = find_batch(found++); if (rc) return rc; }
@@ -466,7 +618,7 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     const bool final = idx_end == starts.size();
     MK_GUN_HIP(mk_gun_grow(&R.h_pieces, &R.hpieces_cap, np, true));
     MK_GUN_HIP(mk_gun_grow(&R.d_pieces, &R.pieces_cap, np));
-    uint64_t nsyms = 0;
+    uint64_t nsyms = 0, nslots = 0;
     for (uint32_t k = 0; k < np; k++) {
       mk_gun_piece &P = R.h_pieces[k];
       memset(&P, 0, sizeof P);
@@ -483,14 +635,22 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
       P.first = idx + k == 0;
       P.sym_off = nsyms;
       nsyms += (cap + 7u) & ~(uint64_t)7u;
+      if (members) { /* a member takes 20 compressed bytes at least */
+        P.kind = (kinds[idx + k] ? MK_GUN_K_MEMBER : 0u) | (idx + k + 1 < starts.size() && kinds[idx + k + 1] ? MK_GUN_K_NEXT_MEMBER : 0u);
+        P.mem_cap = (uint32_t)(covered / 20u + 2u);
+        P.mem_off = nslots;
+        nslots += P.mem_cap;
+      }
     }
+    if (members) MK_GUN_HIP(mk_gun_grow(&R.d_mems, &R.mems_cap, nslots));
     MK_GUN_HIP(mk_gun_grow(&R.d_syms, &R.syms_cap, nsyms));
     MK_GUN_HIP(mk_gun_grow(&R.d_win, &R.win_cap, ((uint64_t)np + 1u) * MK_GUN_WINDOW));
     rc = ensure_uploaded(R.h_pieces[np - 1].end == MK_GUN_NONE ? total : shift + (R.h_pieces[np - 1].end >> 3) + 4096u);
     if (rc) return rc;
     MK_GUN_HIP(hipMemcpyAsync(R.d_pieces, R.h_pieces, (size_t)np * sizeof(mk_gun_piece), hipMemcpyHostToDevice, R.S));
     MK_GUN_HIP(hipEventRecord(R.ev_t[2], R.S));
-    hipLaunchKernelGGL(mk_gun_decode_kernel, dim3((np + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, R.S, (const uint8_t *)R.d_comp, shift, pay_len, R.d_pieces, np, R.d_syms);
+    hipLaunchKernelGGL(members ? mk_gun_decode_kernel<true> : mk_gun_decode_kernel<false>, dim3((np + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, R.S,
+                       (const uint8_t *)R.d_comp, shift, pay_len, R.d_pieces, np, R.d_syms, R.d_mems);
     MK_GUN_HIP(hipGetLastError());
     MK_GUN_HIP(hipEventRecord(R.ev_t[3], R.S));
     MK_GUN_HIP(hipMemcpyAsync(R.h_pieces, R.d_pieces, (size_t)np * sizeof(mk_gun_piece), hipMemcpyDeviceToHost, R.S));
@@ -500,9 +660,10 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     res.decode_ms += ms;
     res.nbatches++;
     uint64_t ntext = 0;
+    uint32_t nrec = 0;
     for (uint32_t k = 0; k < np; k++) {
       mk_gun_piece &P = R.h_pieces[k];
-      if (pieces_out) pieces_out->push_back(mk_gunzip_piece{P.start, P.len});
+      if (pieces_out) pieces_out->push_back(mk_gunzip_piece{P.start | (P.kind & MK_GUN_K_MEMBER ? MK_GUNZIP_PIECE_MEMBER : 0u), P.len});
       res.npieces++;
       if (P.status) {
         (void)hipStreamSynchronize(R.copy);
@@ -510,13 +671,41 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
         return MK_OK;
       }
       if (P.len > P.cap) { snprintf(R.err, sizeof R.err, "piece %llu reports more symbols than its capacity", (unsigned long long)(idx + k)); return MK_ERR_HIP; }
+      if (P.nmem > P.mem_cap) { snprintf(R.err, sizeof R.err, "piece %llu reports more members than it has room for", (unsigned long long)(idx + k)); return MK_ERR_HIP; }
       P.text_off = MK_FQ_CARRY + ntext;
       ntext += P.len;
+      P.rec_off = nrec;
+      nrec += P.nmem;
     }
     /* chain, resolve, CRC */
-    const uint32_t nseg = (uint32_t)((ntext + MK_GUN_CRC_SEG - 1) / MK_GUN_CRC_SEG);
     MK_GUN_HIP(mk_gun_grow(&R.d_text, &R.text_cap, mk_fq_buf_bytes(MK_FQ_CARRY + ntext)));
     MK_GUN_HIP(hipMemcpyAsync(R.d_pieces, R.h_pieces, (size_t)np * sizeof(mk_gun_piece), hipMemcpyHostToDevice, R.S));
+    if (nrec) { /* the members that ended in this batch: their ends in its text, their trailers */
+      MK_GUN_HIP(mk_gun_grow(&R.d_dense, &R.dense_cap, nrec));
+      MK_GUN_HIP(mk_gun_grow(&R.h_dense, &R.hdense_cap, nrec, true));
+      hipLaunchKernelGGL(mk_gun_members_kernel, dim3(np), dim3(64), 0, R.S, (const mk_gun_piece *)R.d_pieces, (const mk_gun_member *)R.d_mems, R.d_dense);
+      MK_GUN_HIP(hipGetLastError());
+      MK_GUN_HIP(hipMemcpyAsync(R.h_dense, R.d_dense, (size_t)nrec * sizeof(mk_gun_member), hipMemcpyDeviceToHost, R.S));
+      MK_GUN_HIP(hipStreamSynchronize(R.S));
+    }
+    /* one segment per member range of the batch's text, split where it would exceed 1 GiB; empty members have one, the open
+     * range behind the last end has one when it holds text */
+    segs.clear();
+    {
+      uint64_t a = 0;
+      for (uint32_t m = 0; m <= nrec; m++) {
+        const uint64_t e = m < nrec ? R.h_dense[m].at : ntext;
+        if (e < a || e > ntext) { snprintf(R.err, sizeof R.err, "member ends out of order in batch %llu", (unsigned long long)bt); return MK_ERR_HIP; }
+        if (m == nrec && e == a) break;
+        do {
+          const uint64_t n = std::min<uint64_t>(MK_GUN_CRC_SEG, e - a);
+          const bool closes = m < nrec && a + n == e;
+          segs.push_back(mk_gun_member{closes ? 1u : 0u, closes ? R.h_dense[m].crc32 : 0u, closes ? R.h_dense[m].isize : 0u, (uint32_t)n});
+          a += n;
+        } while (a < e);
+      }
+    }
+    const uint32_t nseg = (uint32_t)segs.size();
     MK_GUN_HIP(hipMemcpyAsync(R.d_win, R.d_wcarry, MK_GUN_WINDOW, hipMemcpyDeviceToDevice, R.S));
     MK_GUN_HIP(hipEventRecord(R.ev_t[4], R.S));
     hipLaunchKernelGGL(mk_gun_chain_kernel, dim3(1), dim3(1024), 0, R.S, (const mk_gun_piece *)R.d_pieces, np, (const uint16_t *)R.d_syms, R.d_win);
@@ -530,11 +719,13 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
       MK_GUN_HIP(mk_gun_grow(&R.d_crctab, &R.crctab_cap, tab_bytes));
       mk_infl_blk *tab = (mk_infl_blk *)R.h_crctab;
       uint32_t *slice0s = (uint32_t *)(R.h_crctab + mk_gz_slice0_at(nseg));
+      uint64_t at = 0;
       for (uint32_t f = 0; f < nseg; f++) {
-        const uint64_t at = (uint64_t)f * MK_GUN_CRC_SEG, n = std::min<uint64_t>(MK_GUN_CRC_SEG, ntext - at);
-        tab[f] = mk_infl_blk{0u, 0u, (uint32_t)(MK_FQ_CARRY + at), (uint32_t)n, 0u};
+        const uint32_t n = segs[f].pad;
+        tab[f] = mk_infl_blk{0u, 0u, (uint32_t)(MK_FQ_CARRY + at), n, 0u};
         slice0s[f] = nslices;
-        nslices += mk_gz_slices((uint32_t)n);
+        nslices += mk_gz_slices(n);
+        at += n;
       }
       slice0s[nseg] = nslices;
       /* the work words: status[nseg] (zeros) | crc[nseg] | slice registers[nslices] */
@@ -544,7 +735,7 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
       MK_GUN_HIP(hipMemsetAsync(R.d_crcwork, 0, (size_t)nseg * sizeof(uint32_t), R.S));
       const mk_infl_blk *d_tab = (const mk_infl_blk *)R.d_crctab;
       const uint32_t *d_slice0s = (const uint32_t *)(R.d_crctab + mk_gz_slice0_at(nseg));
-      hipLaunchKernelGGL(mk_crc32_files_kernel, dim3((nslices + 3u) / 4u), dim3(256), 0, R.S, (const uint8_t *)R.d_text, d_tab, d_slice0s, nseg, nslices, R.d_crcwork + 2u * (size_t)nseg);
+      if (nslices) hipLaunchKernelGGL(mk_crc32_files_kernel, dim3((nslices + 3u) / 4u), dim3(256), 0, R.S, (const uint8_t *)R.d_text, d_tab, d_slice0s, nseg, nslices, R.d_crcwork + 2u * (size_t)nseg);
       hipLaunchKernelGGL(mk_crc32_combine_kernel, dim3((nseg + 63u) / 64u), dim3(64), 0, R.S, d_tab, d_slice0s, nseg, (const uint32_t *)(R.d_crcwork + 2u * (size_t)nseg), R.d_crcwork, R.d_crcwork + nseg);
       MK_GUN_HIP(hipGetLastError());
       MK_GUN_HIP(hipMemcpyAsync(R.h_crc, R.d_crcwork + nseg, (size_t)nseg * sizeof(uint32_t), hipMemcpyDeviceToHost, R.S));
@@ -557,15 +748,24 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     MK_GUN_HIP(hipEventElapsedTime(&ms, R.ev_t[4], R.ev_t[5]));
     res.resolve_ms += ms;
     for (uint32_t f = 0; f < nseg; f++) {
-      const uint64_t n = std::min<uint64_t>(MK_GUN_CRC_SEG, ntext - (uint64_t)f * MK_GUN_CRC_SEG);
+      const uint64_t n = segs[f].pad;
       crc = mk_crc_concat(crc, R.h_crc[f], n);
+      crc_len += n;
+      if (segs[f].at) { /* the member ends here: its own trailer */
+        if (!member_status) member_status = (uint32_t)crc_len != segs[f].isize ? MK_INFL_OUTPUT_LEN : crc != segs[f].crc32 ? MK_INFL_CRC : MK_INFL_OK;
+        res.members++;
+        crc = 0;
+        crc_len = 0;
+      }
     }
     res.text_len += ntext;
     idx = idx_end;
   }
   MK_GUN_HIP(hipStreamSynchronize(R.S));
   MK_GUN_HIP(hipStreamSynchronize(R.copy));
-  if ((uint32_t)res.text_len != info.isize) res.status = MK_INFL_OUTPUT_LEN;
+  res.members++; /* the last one, whose trailer lies behind the payload */
+  if (member_status) res.status = member_status;
+  else if ((uint32_t)crc_len != info.isize) res.status = MK_INFL_OUTPUT_LEN;
   else if (crc != info.crc32) res.status = MK_INFL_CRC;
   return MK_OK;
 }
@@ -604,6 +804,7 @@ extern "C" int mk_inflate_stream(mk_inflate *h, const uint8_t *comp, size_t comp
   *text_len = res.text_len;
   *status = res.status;
   h->inflate_ms = res.find_ms + res.decode_ms + res.resolve_ms;
+  h->stream_members = res.members;
   if (pieces && !tab.empty()) {
     pieces->v = (mk_gunzip_piece *)malloc(tab.size() * sizeof(mk_gunzip_piece));
     if (!pieces->v) return MK_ERR_NOMEM;
@@ -611,6 +812,12 @@ extern "C" int mk_inflate_stream(mk_inflate *h, const uint8_t *comp, size_t comp
     pieces->n = tab.size();
   }
   if (!fits && !res.status) return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_stream: the text has %llu bytes, cap is %llu", (unsigned long long)res.text_len, (unsigned long long)cap);
+  return MK_OK;
+}
+
+extern "C" int mk_inflate_stream_members(mk_inflate *h, uint64_t *members) {
+  if (!h || !members) return MK_ERR_ARG;
+  *members = h->stream_members;
   return MK_OK;
 }
 
@@ -719,13 +926,13 @@ extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_g
   (void)hipStreamSynchronize(S);
   stats.pieces = res.npieces; stats.batches = res.nbatches; stats.comp_bytes = size; stats.text_bytes = res.text_len;
   stats.find_ms = res.find_ms; stats.decode_ms = res.decode_ms; stats.resolve_ms = res.resolve_ms; stats.t_read_s = res.t_read_s;
-  stats.bad_piece = res.bad_piece; stats.bad_status = res.status;
+  stats.bad_piece = res.bad_piece; stats.bad_status = res.status; stats.members = (uint32_t)std::min<uint64_t>(res.members, 0xffffffffu);
   stats.t_total_s = mk_now_s() - t_begin;
   if (st) *st = stats;
   if (rc == MK_ERR_FORMAT && long_line) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "a FASTQ line of 4095 characters or more"); return rc; }
   if (rc) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", R.err); return rc; }
   if (res.status) {
-    snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "gzip stream, piece %lld: %s", (long long)res.bad_piece, mk_inflate_status_text(res.status));
+    snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "gzip stream, piece %lld: %s", (long long)res.bad_piece, mk_gunzip_status_text(res.status));
     return MK_ERR_FORMAT;
   }
   return MK_OK;

@@ -805,6 +805,7 @@ struct mk_inflate {
   mk_fq_res *d_res = nullptr, *h_res = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   double inflate_ms = 0.0, frame_ms = 0.0;
+  uint64_t stream_members = 0; /* of the last mk_inflate_stream */
   char err[256] = {0};
 };
 

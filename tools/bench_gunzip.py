@@ -7,11 +7,17 @@ uncompressed file; prints one JSON line.  Built on tools/bench_bgzf.py's plan.
 The input is bench.py's read stream (mk_synth_fastq_write_mt, same seed and read length) compressed as ONE gzip member with zlib at
 level 1 and level 6.  Per level the legs run --runs times taking turns, each from process start to the directory on disk; medians
 are reported and the sketch directories must be byte-equal.  Then the span size S is timed at 128 KiB .. 1 MiB on the last level's
-file, and mk_inflate_stream's piece table gives the largest text-to-compressed ratio any piece showed (what R must stay above)."""
+file, and mk_inflate_stream's piece table gives the largest text-to-compressed ratio any piece showed (what R must stay above).
+
+--members N[,N...]: the same reads as a CONCATENATION of N equal members (cut at byte offsets, so records straddle the boundaries), per
+level and N: `--device-gunzip --gunzip-members`, the run without switches and, with --parent-cli, that binary with
+`--device-gunzip` (which falls back to zcat for more than one member), taking turns; with --rocprof one more run per file under
+`rocprofv3 --kernel-trace --stats`, whose kernel totals go into the JSON line and, as CSV, into that directory."""
 import argparse
 import filecmp
 import json
 import os
+import re
 import shutil
 import statistics
 import subprocess
@@ -43,6 +49,79 @@ def compress(args):
     return os.path.getsize(dst)
 
 
+def compress_part(args):
+    src, at, n, level = args
+    with open(src, "rb") as f:
+        f.seek(at)
+        c = zlib.compressobj(level, zlib.DEFLATED, 31)
+        return c.compress(f.read(n)) + c.flush()
+
+
+def write_members(src, dst, level, members, ex):
+    """src as `members` gzip members of equal text size, one behind the other"""
+    size = os.path.getsize(src)
+    cuts = [size * k // members for k in range(members + 1)]
+    with open(dst, "wb") as g:
+        for part in ex.map(compress_part, [(src, a, b - a, level) for a, b in zip(cuts, cuts[1:])], chunksize=max(1, members // 64)):
+            g.write(part)
+    return os.path.getsize(dst)
+
+
+def kernel_totals(directory, name):
+    """{kernel: total ms} from the kernel_stats CSV rocprofv3 wrote for -o `name`; {} when there is none"""
+    import csv
+    import glob
+    out = {}
+    for path in glob.glob(os.path.join(directory, "**", name + "_kernel_stats.csv"), recursive=True):
+        for row in csv.DictReader(open(path)):
+            m = re.search(r"\bmk_[a-z0-9_]+", row.get("Name", ""))  # (names come with return type, namespace and argument list)
+            if m:
+                out[m.group(0)] = round(out.get(m.group(0), 0.0) + float(row["TotalDurationNs"]) / 1e6, 3)
+    return out
+
+
+def bench_members(a, tmp, shuf, fq, levels, out):
+    text_bytes, bases = os.path.getsize(fq), a.reads * READ_LEN
+    gb = lambda t: round(bases / t / 1e9, 3)
+    leg = lambda ts: {"wall_s": med(ts), "gbases_s": gb(statistics.median(ts)), "runs_s": [round(x, 4) for x in ts]}
+    counts = [int(x) for x in a.members.split(",")]
+    out["members"] = {}
+    gz = os.path.join(tmp, "reads.members.fq.gz")
+    with ProcessPoolExecutor(16) as ex:
+        for lv in levels:
+            for n in counts:
+                comp = write_members(fq, gz, lv, n, ex)
+                print("bench_gunzip: level %d, %d members, %d bytes" % (lv, n, comp), file=sys.stderr, flush=True)
+                dev, zc, par, routes, par_routes = [], [], [], [], []
+                d_dev, d_zc, d_par = os.path.join(tmp, "dev"), os.path.join(tmp, "zc"), os.path.join(tmp, "par")
+                for _ in range(a.runs):
+                    dt, route = run_cli(CLI, shuf, d_dev, gz, ["--device-gunzip", "--gunzip-members"])
+                    assert route and route["route"] == "device-gunzip" and route["members"] == n, route
+                    dev.append(dt); routes.append(route)
+                    dt, route = run_cli(CLI, shuf, d_zc, gz, [])
+                    assert route and route["route"] == "zcat" and "fallback" not in route, route
+                    zc.append(dt)
+                    if a.parent_cli:
+                        dt, route = run_cli(a.parent_cli, shuf, d_par, gz, ["--device-gunzip"])
+                        par.append(dt); par_routes.append(route)
+                k = {f: med([r[f] for r in routes]) for f in ("find_ms", "decode_ms", "resolve_ms", "frame_ms", "read_s", "route_total_s")}
+                e = {"comp_bytes": comp, "pieces": routes[0]["pieces"], "batches": routes[0]["batches"], "members": routes[0]["members"],
+                     "device_gunzip_members": leg(dev), "zcat_route": leg(zc), "kernels_ms": k,
+                     "sketch_dirs_equal": bool(same(d_dev, d_zc) and (not par or same(d_dev, d_par)))}
+                if par:
+                    e["parent_device_gunzip"] = dict(leg(par), route=par_routes[0]["route"], fallback=par_routes[0].get("fallback"))
+                    e["speedup_vs_parent"] = round(statistics.median(par) / statistics.median(dev), 2)
+                if a.rocprof:
+                    os.makedirs(a.rocprof, exist_ok=True)
+                    name = "gunzip_members_l%d_m%d" % (lv, n)
+                    subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", a.rocprof, "-o", name, "--", CLI, "dist", "-L", shuf, "-A",
+                                    "-o", os.path.join(tmp, "prof"), "--quiet", "--slow-exit", "--device-gunzip", "--gunzip-members", gz],
+                                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+                    e["rocprof_kernel_totals_ms"] = kernel_totals(a.rocprof, name)
+                out["members"]["l%d_m%d" % (lv, n)] = e
+    out["ok"] = all(v["sketch_dirs_equal"] for v in out["members"].values())
+
+
 def run_cli(cli, shuf, out, inp, extra):
     shutil.rmtree(out, ignore_errors=True)
     t0 = time.perf_counter()
@@ -71,6 +150,7 @@ def main():
     ap.add_argument("--levels", default="1,6")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--parent-cli", default=None, help="a metakssd binary built from the parent commit: its default route is timed too")
+    ap.add_argument("--members", default=None, help="N[,N...]: the reads as N equal gzip members; times the --gunzip-members route instead of the one-member legs")
     ap.add_argument("--rocprof", default=None, help="directory: one more device-route run per level under `rocprofv3 --kernel-trace --stats`")
     a = ap.parse_args()
     from golden_cases import make_shuf
@@ -88,6 +168,10 @@ def main():
         assert capi.lib.mk_synth_fastq_write_mt(fq.encode(), SEED, 0, a.reads, READ_LEN, 16) == 0
         text_bytes, bases = os.path.getsize(fq), a.reads * READ_LEN
         out["text_bytes"] = text_bytes
+        if a.members:
+            bench_members(a, tmp, shuf, fq, levels, out)
+            print(json.dumps(out))
+            return 0 if out.get("ok") else 1
         gzs = {lv: os.path.join(tmp, "reads.l%d.fq.gz" % lv) for lv in levels}
         with ProcessPoolExecutor(len(levels)) as ex:
             comps = dict(zip(levels, ex.map(compress, [(fq, gzs[lv], lv) for lv in levels])))
