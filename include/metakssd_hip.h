@@ -950,6 +950,32 @@ typedef struct mk_gunzip_stats {
  * reads the file another way.  Engines with MK_OPT_SPLIT_CUS: MK_ERR_STATE.  Error text: mk_bgzf_last_error. */
 int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, uint64_t first_ordinal, mk_gunzip_stats *st);
 
+/* ---- a BATCH of single-member gzip genome files, many wavefronts per file ----------------------------------------
+ * mk_sketch_batch_begin_gz with the decode above in place of one wavefront per file: a wave per span of S compressed bytes finds
+ * block starts, a wave per piece decodes, a workgroup per file hands the windows down its pieces, every piece resolves into the
+ * file's place in the batch's text, and the CRC32 of every text is held against its trailer -- all queued on the engine's stream
+ * between the batch's clear and its FASTA walk, without a wait on the host.  opts: span_bytes (0 = 16 KiB here) and ratio (0 = 16) as
+ * for mk_inflate_stream, batch_spans is ignored, flags must be 0 (MK_ERR_ARG): a concatenation of members is MK_INFL_TRAILING here
+ * as in mk_sketch_batch_begin_gz, and the caller reads such a file another way.  Limits and results of mk_sketch_batch_begin_gz,
+ * and two of its own, MK_ERR_ARG before anything is queued: the spans of all files (a payload of n bytes has ceil(n / S)) are at
+ * most 65 535, and ratio * (the payload bytes + the spans of all files) is at most 2^31 symbols of two bytes.  Statuses per file
+ * through mk_sketch_batch_gz_status, in order of precedence: the first piece in stream order that has one (MK_INFL_MISSED and
+ * MK_INFL_CAPACITY among them), MK_INFL_OUTPUT_LEN, MK_INFL_CRC.  Engines with MK_OPT_SPLIT_CUS: MK_ERR_STATE. */
+#define MK_GUNZIP_BATCH_SPAN_DEFAULT (16u << 10)     /* S when span_bytes is 0: the fastest of 16, 32, 64 and 128 KiB on 1 024 genomes */
+#define MK_GUNZIP_BATCH_SPANS_MAX 65535u             /* spans of a batch: a table slot and a 32 KiB window each */
+#define MK_GUNZIP_BATCH_SYMS_MAX ((uint64_t)1 << 31) /* symbols a batch may need room for: 4 GiB */
+int mk_sketch_batch_begin_gunzip(mk_engine *e, int mode, const mk_gz_file *files, uint32_t nfiles, const mk_gunzip_opts *opts);
+/* pieces every file of the batch the LAST mk_sketch_batch_end handed out was decoded in (zeros when that batch was not begun with
+ * mk_sketch_batch_begin_gunzip) */
+int mk_sketch_batch_gz_pieces(mk_engine *e, uint32_t *pieces, uint32_t nfiles);
+/* mk_inflate_members through the same kernels, for tests and tools: res as there (consumed: up to where the last piece the chain
+ * looked at stopped; pos: the text bytes resolved), and per member the list of its pieces (start bit in its payload, text length)
+ * in pieces_per_member[i] (may be NULL; each list is released with mk_gunzip_pieces_free).  out_host's bytes go up before the
+ * kernels run, so a byte no piece wrote comes back as the caller left it.  opts and the two limits as above. */
+int mk_inflate_members_split(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_gz_member *members, uint32_t nmembers,
+                             const mk_gunzip_opts *opts, uint8_t *out_host, size_t out_cap, mk_gz_member_result *res,
+                             mk_gunzip_pieces *pieces_per_member);
+
 /* distance.out (host).  Options as command_dist_wrapper.c:83-92. */
 typedef struct mk_dist_opts {
   int32_t metric;     /* -M: 0 Jaccard / MashD, 1 containment / AafD */

@@ -187,6 +187,10 @@ def _load():
         "mk_sketch_batch_end": [vp, vp],
         "mk_sketch_batch_begin_gz": [vp, C.c_int, C.POINTER(GzFileC), u32],
         "mk_sketch_batch_gz_status": [vp, vp, u32],
+        "mk_sketch_batch_begin_gunzip": [vp, C.c_int, C.POINTER(GzFileC), u32, C.POINTER(GunzipOptsC)],
+        "mk_sketch_batch_gz_pieces": [vp, vp, u32],
+        "mk_inflate_members_split": [vp, vp, C.c_size_t, C.POINTER(GzMemberC), u32, C.POINTER(GunzipOptsC), vp, C.c_size_t,
+                                     C.POINTER(GzMemberResultC), C.POINTER(GunzipPiecesC)],
         "mk_gzip_scan": [C.c_int, vp, C.c_size_t, C.POINTER(GzipInfoC)],
         "mk_gzip_scan_stream": [C.c_int, vp, C.c_size_t, C.POINTER(GzipInfoC)],
         "mk_inflate_stream": [vp, vp, C.c_size_t, C.POINTER(GzipInfoC), C.POINTER(GunzipOptsC), vp, C.c_size_t, C.POINTER(u64), C.POINTER(i32),
@@ -735,9 +739,11 @@ class Engine:
         self._batches = getattr(self, "_batches", [])
         self._batches.append((keep, n))
 
-    def batch_begin_gz(self, gz_files, mode=MK_MODE_SET, one_buffer=False):
+    def batch_begin_gz(self, gz_files, mode=MK_MODE_SET, one_buffer=False, gunzip=None):
         """mk_sketch_batch_begin_gz over a list of byte strings, each a gzip file mk_gzip_scan accepts.  one_buffer: the files lie in ONE
-        16-byte aligned buffer at 1 KiB-aligned offsets (copied from where they are) instead of separate arrays (packed into staging)."""
+        16-byte aligned buffer at 1 KiB-aligned offsets (copied from where they are) instead of separate arrays (packed into staging).
+        gunzip: a dict of mk_gunzip_opts fields (span_bytes, ratio, flags; may be empty) -> mk_sketch_batch_begin_gunzip, many
+        wavefronts per file."""
         n = len(gz_files)
         files = (GzFileC * n)()
         if one_buffer:
@@ -758,9 +764,19 @@ class Engine:
             files[i].comp = ptrs[i]
             files[i].n = len(t)
             _check(lib.mk_gzip_scan(-1, ptrs[i], len(t), C.byref(files[i].info)))
-        _check(lib.mk_sketch_batch_begin_gz(self.h, mode, files, n), self.h)
+        if gunzip is None:
+            _check(lib.mk_sketch_batch_begin_gz(self.h, mode, files, n), self.h)
+        else:
+            o = GunzipOptsC(gunzip.get("span_bytes", 0), gunzip.get("ratio", 0), gunzip.get("batch_spans", 0), gunzip.get("flags", 0))
+            _check(lib.mk_sketch_batch_begin_gunzip(self.h, mode, files, n, C.byref(o)), self.h)
         self._batches = getattr(self, "_batches", [])
         self._batches.append((keep, n))
+
+    def batch_gz_pieces(self, n):
+        """pieces per file of the batch the last batch_end() handed out (zeros: not begun with gunzip=)"""
+        np_ = np.zeros(max(1, n), dtype=np.uint32)
+        _check(lib.mk_sketch_batch_gz_pieces(self.h, np_.ctypes.data, n), self.h)
+        return [int(x) for x in np_[:n]]
 
     def batch_gz_status(self, n):
         """MK_INFL_* per file of the batch the last batch_end() handed out"""
@@ -1409,9 +1425,11 @@ class Inflate:
         self._check(lib.mk_inflate_blocks(self.h, b.ctypes.data, len(b), arr, n, out.ctypes.data, end, st.ctypes.data))
         return out[:end].tobytes(), [int(x) for x in st[:n]]
 
-    def members(self, comp, table):
+    def members(self, comp, table, split=None, fill=0):
         """mk_inflate_members.  comp: bytes, table: dicts (pay_off, pay_len, out_off, isize, crc32) ->
-        (text bytes, [(status, consumed, pos, crc32) per member])"""
+        (text bytes, [(status, consumed, pos, crc32) per member]).  split: a dict of mk_gunzip_opts fields (span_bytes, ratio, flags)
+        -> mk_inflate_members_split, many wavefronts per member, and a third value: [(start bit, text length) per piece] per member.
+        fill: the byte the text buffer holds where no member wrote."""
         b = np.frombuffer(bytes(comp), dtype=np.uint8)
         n = len(table)
         arr = (GzMemberC * max(1, n))()
@@ -1419,10 +1437,19 @@ class Inflate:
             for f in ("pay_off", "pay_len", "out_off", "isize", "crc32"):
                 setattr(arr[i], f, t[f])
         end = max([t["out_off"] + t["isize"] for t in table] + [0])
-        out = np.zeros(max(1, end), dtype=np.uint8)
+        out = np.full(max(1, end), fill, dtype=np.uint8)
         res = (GzMemberResultC * max(1, n))()
-        self._check(lib.mk_inflate_members(self.h, b.ctypes.data if len(b) else None, len(b), arr, n, out.ctypes.data, end, res))
-        return out[:end].tobytes(), [(int(r.status), int(r.consumed), int(r.pos), int(r.crc32)) for r in res[:n]]
+        if split is None:
+            self._check(lib.mk_inflate_members(self.h, b.ctypes.data if len(b) else None, len(b), arr, n, out.ctypes.data, end, res))
+            return out[:end].tobytes(), [(int(r.status), int(r.consumed), int(r.pos), int(r.crc32)) for r in res[:n]]
+        o = GunzipOptsC(split.get("span_bytes", 0), split.get("ratio", 0), split.get("batch_spans", 0), split.get("flags", 0))
+        lists = (GunzipPiecesC * max(1, n))()
+        rc = lib.mk_inflate_members_split(self.h, b.ctypes.data if len(b) else None, len(b), arr, n, C.byref(o), out.ctypes.data, end, res, lists)
+        pieces = [[(int(p.v[k].start_bit), int(p.v[k].text_len)) for k in range(p.n)] for p in lists[:n]]
+        for i in range(n):
+            lib.mk_gunzip_pieces_free(C.byref(lists[i]))
+        self._check(rc)
+        return out[:end].tobytes(), [(int(r.status), int(r.consumed), int(r.pos), int(r.crc32)) for r in res[:n]], pieces
 
     def stream(self, comp, span_bytes=0, ratio=0, batch_spans=0, cap=None, guard=64, members=False):
         """mk_inflate_stream over a whole gzip file (bytes) -> (text or None, MK_INFL_* status, [(start bit, text length) per piece],

@@ -158,6 +158,8 @@ static int g_device_inflate_q = 0;  /* --device-inflate: a BGZF-compressed FASTQ
                                      * the device (mk_sketch_push_bgzf_q), 11-12 times the zcat pipe on 2 M reads.  Opt-in: without the switch this input keeps zcat */
 static int g_device_gunzip = 0;     /* --device-gunzip: an ordinary single-member .gz FASTQ on the -A reader is inflated by many wavefronts (mk_sketch_push_gzip,
                                      * DESIGN.md 4.14).  Opt-in: without the switch such a file keeps zcat */
+static int g_gz_gunzip = 0;         /* --device-gunzip on a directory of genomes: the gz batches are inflated by many wavefronts per file
+                                     * (mk_sketch_batch_begin_gunzip); decides the genome route when --device-inflate is given too */
 static mk_gunzip_opts g_gunzip_opts; /* --gunzip-span-bytes, --gunzip-ratio, --gunzip-batch-spans (test hooks; 0 = the library's defaults) */
 static uint64_t g_inflate_chunk_bytes = 0; /* --inflate-chunk-kib: text bytes per chunk of the device route (test hook; 0 = the library's default) */
 static int g_timing = 0; /* --timing */
@@ -2947,6 +2949,12 @@ int main(int argc, char **argv) {
   if (!quiet) printf("rand_id=%d\thalf_ctx_len=%d\thashsize=%u\thashlimit=%u\n", P.shuf_id, P.k, P.hashsize, P.hashlimit);
   const double t_shuf = now_s() - t0;
 
+  /* --device-gunzip also plans single-member .gz genomes into gz batches, as --device-inflate does; --no-device-inflate turns both off */
+  if (g_device_gunzip && !g_no_device_inflate) { g_gz_batches = 1; g_gz_gunzip = 1; }
+  /* S and R of that route as the library will clamp them: a batch is planned inside its two limits (mk_sketch_batch_begin_gunzip) */
+  const uint64_t gun_S = g_gunzip_opts.span_bytes ? (g_gunzip_opts.span_bytes < 64u ? 64u : g_gunzip_opts.span_bytes > (1u << 30) ? (1u << 30) : g_gunzip_opts.span_bytes)
+                                                  : MK_GUNZIP_BATCH_SPAN_DEFAULT;
+  const uint64_t gun_R = g_gunzip_opts.ratio ? (g_gunzip_opts.ratio > 65536u ? 65536u : g_gunzip_opts.ratio) : 16u;
   { /* a directory of genomes goes to the device in batches of files, each file with a small table of its own: the engine's
      * hashsize-slot tables (21 GB at L2K11) are then made only if a file falls out of its batch (MK_ENGINE_LAZY_TABLES) */
     int plain = 0;
@@ -2990,6 +2998,8 @@ int main(int argc, char **argv) {
         const int grc = mk_gzip_scan(fd, NULL, (size_t)fst.st_size, &gi);
         close(fd);
         if (grc != MK_OK || !gi.is_single || gi.isize > BATCH_FILE_MAX || gi.isize > g_batch_bytes) continue;
+        if (g_gz_gunzip && ((gi.pay_len + gun_S - 1) / gun_S > MK_GUNZIP_BATCH_SPANS_MAX || (gi.pay_len + (gi.pay_len + gun_S - 1) / gun_S) * gun_R > MK_GUNZIP_BATCH_SYMS_MAX))
+          continue; /* (too large for a batch of its own at this span and ratio) */
         fsize[i] = (uint64_t)fst.st_size; gz_isize[i] = gi.isize; elig[i] = 2; n_elig++;
         continue;
       }
@@ -3099,8 +3109,15 @@ int main(int argc, char **argv) {
       size_t at = 0;
       int n = 0;
       size_t text_at = 0;
+      uint64_t gun_spans = 0, gun_units = 0; /* --device-gunzip: spans and (bytes + spans) so far, from the files' sizes (a payload is shorter) */
       const int gz = elig[i] == 2; /* a batch holds files of one kind; its budget is counted in TEXT bytes either way */
       while (i + n < files.n && elig[i + n] == elig[i] && n < g_batch_files && (n == 0 || text_at + (gz ? gz_isize[i + n] : fsize[i + n]) <= g_batch_bytes)) {
+        if (gz && g_gz_gunzip) {
+          const uint64_t ns = (fsize[i + n] + gun_S - 1) / gun_S;
+          if (n && (gun_spans + ns > MK_GUNZIP_BATCH_SPANS_MAX || (gun_units + fsize[i + n] + ns) * gun_R > MK_GUNZIP_BATCH_SYMS_MAX)) break;
+          gun_spans += ns;
+          gun_units += fsize[i + n] + ns;
+        }
         foff[i + n] = at;
         if (gz) at += ((size_t)fsize[i + n] + 1023u) & ~(size_t)1023u; /* the file's bytes as they are */
         else if (batch_rows) { /* its place: the rows its text can give at most */
@@ -3161,8 +3178,8 @@ int main(int argc, char **argv) {
     mk_batch_file *bf = calloc((size_t)g_batch_files, sizeof *bf);
     mk_batch_result *bres = calloc((size_t)g_batch_files, sizeof *bres);
     mk_gz_file *gzf = calloc((size_t)g_batch_files, sizeof *gzf);
-    uint32_t *gzst = calloc((size_t)g_batch_files, sizeof *gzst);
-    if (!bf || !bres || !gzf || !gzst) die("out of memory");
+    uint32_t *gzst = calloc((size_t)g_batch_files, sizeof *gzst), *gzpc = calloc((size_t)g_batch_files, sizeof *gzpc);
+    if (!bf || !bres || !gzf || !gzst || !gzpc) die("out of memory");
     int fly[2], nfly = 0, done_files = 0;
     const int btrace = getenv("MK_BATCH_TRACE") != NULL;
     #define BATCH_END_OLDEST() do { \
@@ -3173,13 +3190,14 @@ int main(int argc, char **argv) {
       if (btrace) fprintf(stderr, "[batch %d] end: called %.3f returned %.3f ms\n", bj_->batch, (tf_ - g_t0) * 1e3, (now_s() - g_t0) * 1e3); \
       if (rc != MK_OK) die("mk_sketch_batch_end failed (%d): %s", rc, mk_last_error(c.eng)); \
       if (bj_->gz && bj_->nsub) (void)mk_sketch_batch_gz_status(c.eng, gzst, (uint32_t)bj_->nsub); \
+      if (bj_->gz && bj_->nsub && g_gz_gunzip) (void)mk_sketch_batch_gz_pieces(c.eng, gzpc, (uint32_t)bj_->nsub); \
       for (int k_ = 0; k_ < bj_->n; k_++) { \
         const char *path_ = files.v[bj_->first + k_]; \
         const int p_ = bj_->gz ? gzpos[bj_->first + k_] : k_; /* its result in bres */ \
         /* a gzip file the device route gave up with a status (more members behind the first, damage): again through zcat, which alone \
          * decides whether the file is damaged -- with the messages and the exit status it has always had */ \
         const int gzfall_ = bj_->gz && p_ >= 0 && gzst[p_] != 0; \
-        if (gzfall_) { grew[bj_->first + k_] = 1; g_gz_fallback = mk_inflate_status_text((int)gzst[p_]); } \
+        if (gzfall_) { grew[bj_->first + k_] = 1; g_gz_fallback = g_gz_gunzip ? mk_gunzip_status_text((int)gzst[p_]) : mk_inflate_status_text((int)gzst[p_]); } \
         if (priv[bj_->first + k_]) { free(priv[bj_->first + k_]); priv[bj_->first + k_] = NULL; } \
         if (grew[bj_->first + k_]) { /* longer than its place: alone, from the whole file, where it stands in the order */ \
           mk_result res_; \
@@ -3191,7 +3209,10 @@ int main(int argc, char **argv) {
           if (!quiet) printf("%d/%d decomposing %s\r", ++done_files, files.n, path_); \
           continue; \
         } \
-        if (bj_->gz) { \
+        if (bj_->gz && g_gz_gunzip) { \
+          if (g_timing) printf("{\"input\": \"%s\", \"route\": \"device-gunzip\", \"pieces\": %u, \"comp_bytes\": %llu, \"text_bytes\": %llu}\n", path_, gzpc[p_], \
+                               (unsigned long long)fsize[bj_->first + k_], (unsigned long long)gz_isize[bj_->first + k_]); \
+        } else if (bj_->gz) { \
           mk_bgzf_stats gs_; \
           memset(&gs_, 0, sizeof gs_); \
           gs_.blocks = 1; gs_.chunks = 1; gs_.comp_bytes = fsize[bj_->first + k_]; gs_.text_bytes = gz_isize[bj_->first + k_]; \
@@ -3261,7 +3282,10 @@ int main(int argc, char **argv) {
       if (c.t_first_push == 0) c.t_first_push = now_s() - g_t0;
       {
         const double tb = now_s();
-        if (bj->gz) rc = nsub ? mk_sketch_batch_begin_gz(c.eng, mode, gzf, (uint32_t)nsub) : MK_OK;
+        if (bj->gz && g_gz_gunzip) {
+          const mk_gunzip_opts go = {g_gunzip_opts.span_bytes, g_gunzip_opts.ratio, 0u, 0u}; /* (members are out of scope in batches: such a file falls back) */
+          rc = nsub ? mk_sketch_batch_begin_gunzip(c.eng, mode, gzf, (uint32_t)nsub, &go) : MK_OK;
+        } else if (bj->gz) rc = nsub ? mk_sketch_batch_begin_gz(c.eng, mode, gzf, (uint32_t)nsub) : MK_OK;
         else rc = batch_rows ? mk_sketch_batch_begin_rows(c.eng, mode, rows_format, bf, (uint32_t)bj->n) : mk_sketch_batch_begin(c.eng, mode, bf, (uint32_t)bj->n);
         t_batch_begin += now_s() - tb;
         nbatches_done++;

@@ -153,6 +153,15 @@ __global__ void __launch_bounds__(256) mk_b_gz_status_kernel(const mk_batch_dev 
   b.stat[f].pad[0] = st;
   if (st) const_cast<mk_bfile *>(b.files)[f].text_len = 0ull;
 }
+/* the same behind mk_gb_launch (many waves per file), whose piece counts travel beside the status */
+__global__ void __launch_bounds__(256) mk_b_gunzip_status_kernel(const mk_batch_dev b, const uint32_t *gz_status, const uint32_t *gz_pieces) {
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= b.nfiles) return;
+  const uint32_t st = gz_status[f];
+  b.stat[f].pad[0] = st;
+  b.stat[f].pad[1] = gz_pieces[f];
+  if (st) const_cast<mk_bfile *>(b.files)[f].text_len = 0ull;
+}
 
 /* ---- a candidate's file and its table ---------------------------------------------------------------------------------------
  * counted upsert into the table of the file that row `row` belongs to: linear probing from a multiplicative hash (the order of

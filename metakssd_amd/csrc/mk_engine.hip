@@ -145,6 +145,7 @@ struct mk_engine {
   uint64_t batch_begun = 0, batch_ended = 0;
   int batch_tb_opt = 0;                /* MK_OPT_BATCH_TAB_BITS: 0 = by the largest file of the batch */
   std::vector<uint32_t> gz_status;     /* MK_INFL_* per file of the batch mk_sketch_batch_end handed out last (mk_sketch_batch_gz_status) */
+  std::vector<uint32_t> gz_pieces;     /* ... and the pieces it was decoded in (mk_sketch_batch_gz_pieces; zeros: not a gunzip batch) */
   const mk_batch_dev *cur_batch = nullptr; /* set around the scan launches of a batch */
 
   int mode = -1;
@@ -2151,7 +2152,9 @@ struct mk_bctx {
   mk_dbuf comp, gztab, gzwork;                     /* mk_sketch_batch_begin_gz: compressed bytes, member table, statuses and slice CRCs */
   void *h_comp = nullptr; size_t h_comp_cap = 0;   /* pinned: the compressed bytes of files that do not lie in one stretch */
   void *h_gztab = nullptr; size_t h_gztab_cap = 0; /* pinned: the member table */
+  mk_dbuf gbtab, gbscratch, gbwin, gbsyms;         /* mk_sketch_batch_begin_gunzip: span table of the files, of the spans, windows, symbols */
   bool gz = false;                                 /* the texts were made on the device: a file sketched alone fetches its text from there */
+  bool gunzip = false;                             /* ... by many waves per file: pad[1] of a file's mk_bstat is its piece count */
   std::vector<uint64_t> text_off;                  /* per file of a gz batch: its place in `text` */
   void *h_desc = nullptr; size_t h_desc_cap = 0;   /* pinned: what goes up in one small copy (descriptor, files, seg0s, row0s) */
   void *h_stat = nullptr; size_t h_stat_cap = 0;   /* pinned: what comes back first (per-file status, per-component sizes, totals) */
@@ -2192,7 +2195,7 @@ static int mk_pinned_fit(mk_engine *e, void **p, size_t *cap, size_t need) {
 }
 static void mk_bctx_free(mk_bctx *c) {
   if (!c) return;
-  for (mk_dbuf *b : {&c->text, &c->stream, &c->sum, &c->desc, &c->zero, &c->map, &c->list, &c->bcur, &c->comp, &c->gztab, &c->gzwork}) hipFree(b->p);
+  for (mk_dbuf *b : {&c->text, &c->stream, &c->sum, &c->desc, &c->zero, &c->map, &c->list, &c->bcur, &c->comp, &c->gztab, &c->gzwork, &c->gbtab, &c->gbscratch, &c->gbwin, &c->gbsyms}) hipFree(b->p);
   if (c->h_comp) hipHostFree(c->h_comp);
   if (c->h_gztab) hipHostFree(c->h_gztab);
   if (c->h_desc) hipHostFree(c->h_desc);
@@ -2225,7 +2228,9 @@ static uint64_t mk_rows_per_launch(const mk_engine *e, uint32_t row_bases, int t
  * of set-up at the first copy of a process) */
 /* gz != nullptr: the texts are made on the device from single-member gzip files (mk_sketch_batch_begin_gz); files[i].n is then the
  * text's size, the trailer's ISIZE, and files[i].text is not used */
-static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *files, uint32_t nfiles, const uint32_t format, const mk_gz_file *gz = nullptr) {
+/* gun != nullptr (with gz): the texts are made by many waves per file, mk_gb_launch in mk_gz_launch's place (mk_sketch_batch_begin_gunzip) */
+static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *files, uint32_t nfiles, const uint32_t format, const mk_gz_file *gz = nullptr,
+                               const mk_gb_geom *gun = nullptr) {
   if (!e || !files) return MK_ERR_ARG;
   if (format != 0u && format != MK_ROWS_PACKED && format != MK_ROWS_WIDE) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_rows: format MK_ROWS_PACKED or MK_ROWS_WIDE");
   const bool rows = format != 0u;
@@ -2341,6 +2346,17 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
     }
     if (comp_span >= (1ull << 31)) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_gz: %llu compressed bytes (below 2 GiB a batch)", (unsigned long long)comp_span);
   }
+  uint64_t gb_spans = 0, gb_syms = 0;
+  if (gun) { /* refused before anything is allocated or queued */
+    for (uint32_t i = 0; i < nfiles; i++) {
+      const uint64_t ns = mk_gb_spans(gz[i].info.pay_len, gun->S);
+      gb_spans += ns;
+      gb_syms += (gz[i].info.pay_len + ns) * gun->R;
+    }
+    if (gb_spans > MK_GB_SPANS_MAX || gb_syms > MK_GB_SYMS_MAX)
+      return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_gunzip: %llu spans and %llu symbols (at most %u and %llu a batch)", (unsigned long long)gb_spans,
+                     (unsigned long long)gb_syms, MK_GB_SPANS_MAX, (unsigned long long)MK_GB_SYMS_MAX);
+  }
   const uint64_t text_span = rows ? 0 : one_copy ? (uint64_t)(files[nfiles - 1].text - files[0].text) + files[nfiles - 1].n : toff;
   const uint64_t total_rows = soff / (rows ? MK_PACKED_PITCH : pitch);
   const uint32_t nseg_total = seg;
@@ -2392,8 +2408,16 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
   if (gz) {
     if ((rc = mk_dbuf_fit(e, c->comp, (size_t)comp_span + 64))) return rc;
     if ((rc = mk_dbuf_fit(e, c->gztab, mk_gz_table_bytes(nfiles)))) return rc;
-    if ((rc = mk_dbuf_fit(e, c->gzwork, mk_gz_work_words(nfiles, nslices) * 4))) return rc;
-    if ((rc = mk_pinned_fit(e, &c->h_gztab, &c->h_gztab_cap, mk_gz_table_bytes(nfiles)))) return rc;
+    if ((rc = mk_dbuf_fit(e, c->gzwork, (gun ? mk_gb_work_words(nfiles, nslices) : mk_gz_work_words(nfiles, nslices)) * 4))) return rc;
+    /* (gunzip: the files' span table travels behind the member table, in the same copy) */
+    const size_t gztab_bytes = mk_gz_table_bytes(nfiles) + (gun ? (size_t)nfiles * sizeof(mk_gb_file) : 0u);
+    if ((rc = mk_pinned_fit(e, &c->h_gztab, &c->h_gztab_cap, gztab_bytes))) return rc;
+    if (gun) {
+      if ((rc = mk_dbuf_fit(e, c->gbtab, (size_t)nfiles * sizeof(mk_gb_file)))) return rc;
+      if ((rc = mk_dbuf_fit(e, c->gbscratch, mk_gb_scratch_bytes(gb_spans)))) return rc;
+      if ((rc = mk_dbuf_fit(e, c->gbwin, mk_gb_win_bytes(gb_spans)))) return rc;
+      if ((rc = mk_dbuf_fit(e, c->gbsyms, mk_gb_sym_bytes(gb_syms)))) return rc;
+    }
     if (!comp_in_place && (rc = mk_pinned_fit(e, &c->h_comp, &c->h_comp_cap, (size_t)comp_span + 64))) return rc;
     mk_infl_blk *tab = (mk_infl_blk *)c->h_gztab;
     uint32_t *slice0s = (uint32_t *)((uint8_t *)c->h_gztab + mk_gz_slice0_at(nfiles));
@@ -2408,6 +2432,10 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
       if (!comp_in_place) memcpy((uint8_t *)c->h_comp + coff[i], gz[i].comp, (size_t)gz[i].n);
     }
     slice0s[nfiles] = s0;
+    if (gun) {
+      uint64_t ns = 0, nsy = 0;
+      (void)mk_gb_plan(tab, nfiles, *gun, (mk_gb_file *)((uint8_t *)c->h_gztab + mk_gz_table_bytes(nfiles)), &ns, &nsy); /* (the counts held above) */
+    }
   }
   const double tr1 = trace ? mk_tick_now() : 0.0;
   {
@@ -2445,6 +2473,7 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
   c->hb = *hb;
   c->mode = mode; c->nfiles = nfiles; c->rows = rows; c->format = format; c->rows_src = rows ? (rows_dev ? rows_dev : (const uint8_t *)c->stream.p) : nullptr;
   c->gz = gz != nullptr;
+  c->gunzip = gun != nullptr;
   c->files.assign(files, files + nfiles);
   const mk_batch_dev *dbatch = (const mk_batch_dev *)dd;
   hipStream_t s = e->stream;
@@ -2471,6 +2500,7 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
   } else if (gz) {
     MK_HIP(e, hipMemcpyAsync(c->comp.p, comp_in_place ? (const void *)gz[0].comp : (const void *)c->h_comp, (size_t)comp_span, hipMemcpyHostToDevice, s));
     MK_HIP(e, hipMemcpyAsync(c->gztab.p, c->h_gztab, mk_gz_table_bytes(nfiles), hipMemcpyHostToDevice, s));
+    if (gun) MK_HIP(e, hipMemcpyAsync(c->gbtab.p, (const uint8_t *)c->h_gztab + mk_gz_table_bytes(nfiles), (size_t)nfiles * sizeof(mk_gb_file), hipMemcpyHostToDevice, s));
   } else if (one_copy) {
     if (text_span) MK_HIP(e, hipMemcpyAsync(c->text.p, files[0].text, (size_t)text_span, hipMemcpyHostToDevice, s));
   } else {
@@ -2482,8 +2512,15 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
   hipLaunchKernelGGL(mk_b_clear_kernel, dim3(wide), dim3(256), 0, s, (uint4 *)c->zero.p, (unsigned long long)(zero_bytes / 16u), (uint4 *)c->map.p,
                      (unsigned long long)(N / 2u), (uint4 *)nullptr, 0ull);
   if (gz) { /* the texts: inflate, CRC; a file with a status keeps no text (behind the clear: the status travels in the file's mk_bstat) */
-    MK_HIP(e, mk_gz_launch(s, (const uint8_t *)c->comp.p, c->gztab.p, nfiles, nslices, (uint8_t *)c->text.p, (uint32_t *)c->gzwork.p));
-    hipLaunchKernelGGL(mk_b_gz_status_kernel, dim3((nfiles + 255u) / 256u), dim3(256), 0, s, c->hb, (const uint32_t *)c->gzwork.p);
+    if (gun) {
+      MK_HIP(e, mk_gb_launch(s, (const uint8_t *)c->comp.p, c->gztab.p, (const mk_gb_file *)c->gbtab.p, nfiles, nslices, (uint32_t)gb_spans, *gun, c->gbscratch.p,
+                             (uint16_t *)c->gbsyms.p, (uint8_t *)c->gbwin.p, (uint8_t *)c->text.p, (uint32_t *)c->gzwork.p));
+      hipLaunchKernelGGL(mk_b_gunzip_status_kernel, dim3((nfiles + 255u) / 256u), dim3(256), 0, s, c->hb, (const uint32_t *)c->gzwork.p,
+                         (const uint32_t *)c->gzwork.p + 4u * (size_t)nfiles);
+    } else {
+      MK_HIP(e, mk_gz_launch(s, (const uint8_t *)c->comp.p, c->gztab.p, nfiles, nslices, (uint8_t *)c->text.p, (uint32_t *)c->gzwork.p));
+      hipLaunchKernelGGL(mk_b_gz_status_kernel, dim3((nfiles + 255u) / 256u), dim3(256), 0, s, c->hb, (const uint32_t *)c->gzwork.p);
+    }
   }
   if (!rows) {
     hipLaunchKernelGGL(mk_fab_summary_kernel, dim3((nseg_total + 3u) / 4u), dim3(256), 0, s, (const uint8_t *)c->text.p, c->hb, nseg_total, (mk_fa_sum *)c->sum.p);
@@ -2558,6 +2595,28 @@ extern "C" int mk_sketch_batch_begin_gz(mk_engine *e, int mode, const mk_gz_file
   return mk_batch_begin_impl(e, mode, texts.data(), nfiles, 0u, files);
 }
 
+extern "C" int mk_sketch_batch_begin_gunzip(mk_engine *e, int mode, const mk_gz_file *files, uint32_t nfiles, const mk_gunzip_opts *opts) {
+  if (!e || !files) return MK_ERR_ARG;
+  if (e->scan_stream) return mk_fail(e, MK_ERR_STATE, "mk_sketch_batch_begin_gunzip: MK_OPT_SPLIT_CUS runs the scan on a queue of its own");
+  if (nfiles < 1 || nfiles > MK_BATCH_MAX_FILES) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_gunzip: 1 .. %u files", MK_BATCH_MAX_FILES);
+  mk_gb_geom G;
+  if (!mk_gb_geometry(opts, &G)) return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_gunzip: flags must be 0 (a concatenation of members is MK_INFL_TRAILING in a batch)");
+  std::vector<mk_batch_file> texts(nfiles);
+  for (uint32_t i = 0; i < nfiles; i++) {
+    const mk_gzip_info &gi = files[i].info;
+    if (!files[i].comp || !gi.is_single || gi.isize < 1u || gi.pay_len < 1u || gi.pay_len >= (1ull << 31) || gi.pay_off + gi.pay_len + 8u > files[i].n)
+      return mk_fail(e, MK_ERR_ARG, "mk_sketch_batch_begin_gunzip: file %u: not what mk_gzip_scan accepts", i);
+    texts[i] = mk_batch_file{nullptr, gi.isize};
+  }
+  return mk_batch_begin_impl(e, mode, texts.data(), nfiles, 0u, files, &G);
+}
+
+extern "C" int mk_sketch_batch_gz_pieces(mk_engine *e, uint32_t *pieces, uint32_t nfiles) {
+  if (!e || (!pieces && nfiles)) return MK_ERR_ARG;
+  for (uint32_t i = 0; i < nfiles; i++) pieces[i] = i < e->gz_pieces.size() ? e->gz_pieces[i] : 0u;
+  return MK_OK;
+}
+
 extern "C" int mk_sketch_batch_gz_status(mk_engine *e, uint32_t *status, uint32_t nfiles) {
   if (!e || (!status && nfiles)) return MK_ERR_ARG;
   for (uint32_t i = 0; i < nfiles; i++) status[i] = i < e->gz_status.size() ? e->gz_status[i] : 0u;
@@ -2598,6 +2657,8 @@ extern "C" int mk_sketch_batch_end(mk_engine *e, mk_batch_result *out) {
   size_t n_alone = 0;
   e->gz_status.assign(nfiles, 0u);
   for (uint32_t i = 0; i < nfiles && c->gz; i++) e->gz_status[i] = st[i].pad[0];
+  e->gz_pieces.assign(nfiles, 0u);
+  for (uint32_t i = 0; i < nfiles && c->gunzip; i++) e->gz_pieces[i] = st[i].pad[1];
   std::vector<uint8_t> gz_text; /* a gz batch's file that is sketched alone: its text comes back from the device first */
   for (uint32_t i = 0; i < nfiles; i++) if ((st[i].flags & MK_BF_REDO) && !(st[i].flags & MK_BF_HEADER_END)) n_alone++;
   c->alone_ids.resize(n_alone);

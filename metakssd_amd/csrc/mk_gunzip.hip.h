@@ -171,20 +171,16 @@ __device__ __forceinline__ int64_t mk_gun_seek(mk_zbits &b, const uint8_t *comp,
   return 8 * ((int64_t)base_off - (int64_t)shift);
 }
 
-/* cand[i]: the candidate of span span0 + i (span0 >= 1), MK_GUN_NONE when the span has none.  MEMBERS: the lowest position of
+/* The finder's rule over the bits [lo, hi) of one payload, hi <= 8 * pay_len, by one wave with its LDS L: the lowest position, the
+ * same in every lane, MK_GUN_NONE when there is none (mk_gunzip_batch.hip.h calls it with the payload of the file a span belongs
+ * to).  MEMBERS: the lowest position of
  * either kind -- a block start as ever, or 8 * (a byte q at which a member header of at most MK_GUN_HDR_MAX bytes stands and, at the
  * first bit behind it, a dynamic block header, final or not, that passes the same validation), with MK_GUNZIP_PIECE_MEMBER set.
  * The two never meet at one bit: 0x1f has BFINAL set. */
 template <bool MEMBERS>
-__global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_find_kernel(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len, uint32_t S,
-                                                                          uint64_t span0, uint32_t nspans, uint64_t *cand) {
-  __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t i = blockIdx.x * MK_INFL_WAVES + wave;
-  if (i >= nspans) return;
-  mk_infl_lds &L = lds_all[wave];
-  const uint64_t c = span0 + i, nbits = 8u * pay_len;
-  const uint64_t lo = 8u * c * S, hi = 8u * (c + 1u) * S < nbits ? 8u * (c + 1u) * S : nbits;
+__device__ __forceinline__ uint64_t mk_gun_find_span(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len, uint64_t lo, uint64_t hi,
+                                                     mk_infl_lds &L, uint32_t lane) {
+  const uint64_t nbits = 8u * pay_len;
   const uint32_t *words = (const uint32_t *)comp;
   uint64_t found = MK_GUN_NONE;
   for (uint64_t p0 = lo; p0 < hi && found == MK_GUN_NONE; p0 += 64u) {
@@ -238,19 +234,28 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_find_kernel(const u
       found = member ? cp | MK_GUNZIP_PIECE_MEMBER : cp;
     }
   }
+  return found;
+}
+
+/* cand[i]: the candidate of span span0 + i (span0 >= 1), MK_GUN_NONE when the span has none */
+template <bool MEMBERS>
+__global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_find_kernel(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len, uint32_t S,
+                                                                          uint64_t span0, uint32_t nspans, uint64_t *cand) {
+  __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t i = blockIdx.x * MK_INFL_WAVES + wave;
+  if (i >= nspans) return;
+  const uint64_t c = span0 + i, nbits = 8u * pay_len;
+  const uint64_t lo = 8u * c * S, hi = 8u * (c + 1u) * S < nbits ? 8u * (c + 1u) * S : nbits;
+  const uint64_t found = mk_gun_find_span<MEMBERS>(comp, shift, pay_len, lo, hi, lds_all[wave], lane);
   if (lane == 0u) cand[i] = found;
 }
 
 /* MEMBERS: behind a final block that ends in front of the payload's end the wave reads the member's trailer into a member record,
  * stops where the next piece starts at the header behind it, and otherwise walks that header and decodes on (4.15). */
 template <bool MEMBERS>
-__global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len,
-                                                                            mk_gun_piece *pieces, uint32_t npieces, uint16_t *syms, mk_gun_member *mems) {
-  __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t k = blockIdx.x * MK_INFL_WAVES + wave;
-  if (k >= npieces) return;
-  mk_infl_lds &L = lds_all[wave];
+__device__ __forceinline__ void mk_gun_decode_piece(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len, mk_gun_piece *pieces, uint32_t k,
+                                                    uint16_t *syms, mk_gun_member *mems, mk_infl_lds &L, uint32_t lane) {
   const uint64_t start = mk_uni64(pieces[k].start), end_bit = mk_uni64(pieces[k].end);
   const uint32_t cap = mk_uni(pieces[k].cap), back = mk_uni(pieces[k].first) ? 0u : MK_GUN_WINDOW;
   const bool last_piece = end_bit == MK_GUN_NONE;
@@ -388,6 +393,17 @@ __global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const
     pieces[k].stop = stop_bit != MK_GUN_NONE ? stop_bit : (uint64_t)((int64_t)b.bitpos() + bit0);
     if (MEMBERS) pieces[k].nmem = nmem;
   }
+}
+
+/* one wave per piece of ONE stream (mk_gunzip_batch.hip.h has the kernel for the pieces of many files) */
+template <bool MEMBERS>
+__global__ void __launch_bounds__(64 * MK_INFL_WAVES) mk_gun_decode_kernel(const uint8_t *__restrict__ comp, uint32_t shift, uint64_t pay_len,
+                                                                            mk_gun_piece *pieces, uint32_t npieces, uint16_t *syms, mk_gun_member *mems) {
+  __shared__ mk_infl_lds lds_all[MK_INFL_WAVES];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t k = blockIdx.x * MK_INFL_WAVES + wave;
+  if (k >= npieces) return;
+  mk_gun_decode_piece<MEMBERS>(comp, shift, pay_len, pieces, k, syms, mems, lds_all[wave], lane);
 }
 
 /* win: npieces + 1 windows of 32 KiB; window 0 is W of the piece in front of the batch, window c + 1 becomes W(piece c) */

@@ -40,6 +40,8 @@
  *                        windows: a line of 4095+ characters is refused, the caller takes the host framer for such a file.
  * mk_gunzip.hip.h (included last): ONE gzip member of any size by many waves -- block-start finder, decode to 16-bit symbols with
  *                        markers, window chain, resolve -- around this file's bit reader, table builder and CRC kernels.
+ * mk_gunzip_batch.hip.h (behind it): a BATCH of gzip genome files, many waves per file, as one launch sequence without a host wait:
+ *                        the same finder and decode per (file, span), the piece table and the text offsets made on the device (4.16).
  * Bound of each kernel: DESIGN.md 4.10, 4.12.
  */
 #include <hip/hip_runtime.h>
@@ -1354,3 +1356,4 @@ extern "C" int mk_sketch_push_bgzf_q(mk_engine *e, int fd, size_t size, const mk
 extern "C" const char *mk_bgzf_last_error(void) { return mk_bgzf_err; }
 
 #include "mk_gunzip.hip.h"
+#include "mk_gunzip_batch.hip.h"

@@ -6,8 +6,15 @@ binary (--parent-cli: the parent commit's), and the plain-text directory beside 
 
 The genomes are bench.py's (write_genomes: same pool, same seed), compressed here with `gzip -<level>` per file.  Per geometry
 (L3K10, L2K11) and level the legs run --runs times taking turns, process start to directory on disk by this process's clock;
-medians are reported and the sketch directories of every leg must be byte-equal to the plain-text directory's."""
+medians are reported and the sketch directories of every leg must be byte-equal to the plain-text directory's.
+
+--gunzip adds the route that gives every file many wavefronts (`--device-gunzip`, mk_sketch_batch_begin_gunzip): one
+leg per span size of --span-bytes, beside the others in every turn; the result says pieces per genome, the best span, and that
+span's ratio over the one-wavefront route, the zcat route and the parent's binary.  --json-out keeps what is known after every cell;
+--rocprof then takes one more run per cell under `rocprofv3 --kernel-trace --stats` and gathers the kernels' totals in one CSV."""
 import argparse
+import csv
+import glob
 import filecmp
 import json
 import os
@@ -48,7 +55,12 @@ def main():
     ap.add_argument("--parent-cli", default=None, help="another build's metakssd binary (the parent commit's), run on the same files")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--rocprof", default=None, help="directory: one more device-route run per geometry under `rocprofv3 --kernel-trace --stats`")
+    ap.add_argument("--gunzip", action="store_true", help="a leg per span size with --device-gunzip (many wavefronts per file)")
+    ap.add_argument("--span-bytes", default="16384,32768,65536,131072", help="the span sizes of --gunzip")
+    ap.add_argument("--json-out", default=None, help="file: the result so far, rewritten after every cell")
     a = ap.parse_args()
+    spans = [int(x) for x in a.span_bytes.split(",")] if a.gunzip else []
+    stats_rows = []
     import bench
     from metakssd_amd import capi
     if capi.device_count() < 1:
@@ -85,6 +97,9 @@ def main():
             res = {"plain_text": {"wall_s": round(statistics.median(tp), 4), "genomes_s": round(a.genomes / statistics.median(tp), 1)}, "levels": {}}
             for level, (gd, comp, t_gz) in gzdirs.items():
                 legs = {"device_route": (CLI, ["--device-inflate"]), "no_device_inflate": (CLI, ["--no-device-inflate"])}
+                for S in spans:
+                    legs["gunzip_%d" % S] = (CLI, ["--device-gunzip", "--gunzip-span-bytes", str(S)])
+                pieces = {}
                 if a.parent_cli:
                     legs["parent"] = (a.parent_cli, [])
                 walls = {k: [] for k in legs}
@@ -96,6 +111,9 @@ def main():
                         dt, routes = run_cli(cli, shuf, od, gd, extra)
                         if k == "device_route":
                             assert len(routes) == a.genomes and all(x["route"] == "device-inflate" for x in routes), "the device route was not taken"
+                        if k.startswith("gunzip_"):
+                            assert len(routes) == a.genomes and all(x["route"] == "device-gunzip" and "fallback" not in x for x in routes), "the gunzip route was not taken"
+                            pieces[k] = round(sum(x["pieces"] for x in routes) / len(routes), 1)
                         walls[k].append(dt)
                         equal = equal and same_dirs_names(d_plain, od)
                 med = {k: statistics.median(v) for k, v in walls.items()}
@@ -106,12 +124,44 @@ def main():
                 res["levels"][str(level)]["speedup_vs_no_device_inflate"] = round(med["no_device_inflate"] / med["device_route"], 2)
                 if a.parent_cli:
                     res["levels"][str(level)]["speedup_vs_parent"] = round(med["parent"] / med["device_route"], 2)
-            if a.rocprof:
+                if spans:
+                    cell = res["levels"][str(level)]
+                    best = min(("gunzip_%d" % S for S in spans), key=lambda k: med[k])
+                    for k, v in pieces.items():
+                        cell[k]["pieces_per_genome"] = v
+                    cell["gunzip_best"] = best
+                    cell["gunzip_over_device_route"] = round(med["device_route"] / med[best], 2)
+                    # faster by more than either leg's spread: the slowest gunzip run against the fastest one-wavefront run
+                    cell["gunzip_faster_beyond_spread"] = bool(max(walls[best]) < min(walls["device_route"]))
+                    cell["gunzip_over_no_device_inflate"] = round(med["no_device_inflate"] / med[best], 2)
+                    if a.parent_cli:
+                        cell["gunzip_over_parent"] = round(med["parent"] / med[best], 2)
+                    if a.rocprof:
+                        os.makedirs(a.rocprof, exist_ok=True)
+                        tag = "gunzip_%s_l%d" % (geo, level)
+                        subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", a.rocprof, "-o", tag, "--", CLI, "dist", "-L", shuf, "-o", os.path.join(tmp, "prof"),
+                                        "--quiet", "--slow-exit"] + legs[best][1] + [gd], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
+                        for f in glob.glob(os.path.join(a.rocprof, "**", tag + "_kernel_stats.csv"), recursive=True):
+                            rows = list(csv.reader(open(f)))
+                            if not stats_rows and rows:
+                                stats_rows.append(["cell", "span_bytes"] + rows[0])
+                            stats_rows.extend([["%s_gzip%d" % (geo, level), best.split("_")[1]] + r for r in rows[1:]])
+                if a.json_out:
+                    out["geometries"][geo] = res
+                    with open(a.json_out, "w") as f:
+                        json.dump(out, f)
+                    if stats_rows:
+                        with open(os.path.splitext(a.json_out)[0] + "_kernel_stats.csv", "w", newline="") as f:
+                            csv.writer(f).writerows(stats_rows)
+            if a.rocprof and not spans:
                 os.makedirs(a.rocprof, exist_ok=True)
                 subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", a.rocprof, "-o", "gzfasta_" + geo, "--", CLI, "dist", "-L", shuf, "-o", os.path.join(tmp, "prof"),
                                 "--quiet", "--slow-exit", "--device-inflate", gzdirs[sorted(gzdirs)[-1]][0]], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
             out["geometries"][geo] = res
         out["ok"] = all(v["sketches_equal_plain"] for g in out["geometries"].values() for v in g["levels"].values())
+        if a.json_out:
+            with open(a.json_out, "w") as f:
+                json.dump(out, f)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     print(json.dumps(out))
