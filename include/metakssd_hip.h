@@ -176,12 +176,17 @@ int mk_engine_destroy(mk_engine *e);
  *                   sketches, 0-3 % over twenty, a loss on a throttled GPU -- an option; bench.py times it as a side leg, never as its headline).
  *                   Layout, dump and the result copy of mk_sketch_finish_begin run on the scan queue's units under this option.
  *                   Default 0: one queue, every kernel on the whole device
+ *   MK_OPT_BATCH_HOME_IDS 0 / 4 ..: a cap on the ids that come home in a batch's own launch sequence (a test hook).  0 (default): the
+ *                   engine's rule alone -- half of every table, 8 Mi ids, twice the estimate + 65 536, whichever is least.  Any other
+ *                   value is rounded up to a multiple of 4 and only ever LOWERS what the rule gives; ids beyond it are fetched by a
+ *                   copy inside mk_sketch_batch_end (mk_sketch_batch_home_ids says how many).  1..3 and negative values are
+ *                   MK_ERR_ARG; MK_ERR_STATE while a batch is in flight.  Results do not depend on it
  *   (8 and 9 were MK_OPT_ROWS160 and MK_OPT_BATCH_QUEUES in round 4: a scan kernel that kept a lane's text row in registers and a
  *   second queue for every other batch.  Both measured slower than what they replaced -- profiles/r04_b_kernel_stats_rows160_variant.csv,
  *   profiles/r04_d_config5_two_queues.txt -- and were removed in round 5; the numbers stay retired.)
  * Results are bit-identical for every setting; the tests run both. */
 enum { MK_OPT_SPARSE = 1, MK_OPT_CAND_CAP = 2, MK_OPT_RESULT_CAP = 3, MK_OPT_DIRECT_HOST = 4, MK_OPT_FRONT_BITS = 5, MK_OPT_KEYLIST_CAP = 6,
-       MK_OPT_BATCH_TAB_BITS = 7, MK_OPT_SPLIT_CUS = 10 };
+       MK_OPT_BATCH_TAB_BITS = 7, MK_OPT_SPLIT_CUS = 10, MK_OPT_BATCH_HOME_IDS = 11 };
 int mk_engine_set_option(mk_engine *e, int option, int64_t value);
 int mk_engine_set_stream(mk_engine *e, void *hip_stream);
 int mk_engine_use_own_stream(mk_engine *e);
@@ -317,6 +322,11 @@ int mk_sketch_batch_begin(mk_engine *e, int mode, const mk_batch_file *files, ui
  * batch's tables cannot take is sketched alone from its rows). */
 int mk_sketch_batch_begin_rows(mk_engine *e, int mode, uint32_t format, const mk_batch_file *files, uint32_t nfiles);
 int mk_sketch_batch_end(mk_engine *e, mk_batch_result *out /* [nfiles of the oldest batch] */);
+/* Of the batch the LAST mk_sketch_batch_end handed out: ids that came home in the batch's own launch sequence, and ids that
+ * mk_sketch_batch_end had to fetch by a copy of its own because the batch left more than its pinned block held (0 for nearly every
+ * batch; MK_OPT_BATCH_HOME_IDS).  Files that were sketched alone count in neither; a file that ends inside a header line (MK_ERR_FORMAT) counts with the ids of
+ * the text in front of that line, which the batch wrote and nobody is handed.  Either pointer may be NULL. */
+int mk_sketch_batch_home_ids(mk_engine *e, uint64_t *with_batch, uint64_t *late);
 
 /* pinned host memory for the caller's read batches (hipHostMalloc) */
 int mk_host_alloc(void **p, size_t bytes);

@@ -21,6 +21,7 @@ MK_ROWS_WIDE, MK_WIDE_MAX_BASES = 0x40000000, 240
 MK_OPT_SPARSE, MK_OPT_CAND_CAP, MK_OPT_RESULT_CAP, MK_OPT_DIRECT_HOST, MK_OPT_FRONT_BITS, MK_OPT_KEYLIST_CAP, MK_OPT_BATCH_TAB_BITS = 1, 2, 3, 4, 5, 6, 7
 MK_BEGIN_NOTHING_FOLLOWS = 0x100  # mk_sketch_begin(mode | this): the last sketch of a run on split queues -- its tail on the whole device
 MK_OPT_SPLIT_CUS = 10  # scan kernel on a queue of its own, the rest on this many compute units (two engines in turn: bench.py)
+MK_OPT_BATCH_HOME_IDS = 11  # test hook: a cap on the ids that come home with a batch; mk_sketch_batch_end fetches the rest late
 
 
 class MkError(RuntimeError):
@@ -185,6 +186,7 @@ def _load():
         "mk_sketch_batch_begin_rows": [vp, C.c_int, u32, vp, u32],
         "mk_fasta_pack_rows": [vp, C.c_size_t, C.c_int32, u32, vp, u64, C.POINTER(u64)],
         "mk_sketch_batch_end": [vp, vp],
+        "mk_sketch_batch_home_ids": [vp, C.POINTER(u64), C.POINTER(u64)],
         "mk_sketch_batch_begin_gz": [vp, C.c_int, C.POINTER(GzFileC), u32],
         "mk_sketch_batch_gz_status": [vp, vp, u32],
         "mk_sketch_batch_begin_gunzip": [vp, C.c_int, C.POINTER(GzFileC), u32, C.POINTER(GunzipOptsC)],
@@ -784,8 +786,16 @@ class Engine:
         _check(lib.mk_sketch_batch_gz_status(self.h, st.ctypes.data, n), self.h)
         return [int(x) for x in st[:n]]
 
-    def batch_end(self):
-        """-> per file (status, alone, [ids per component]) of the oldest batch in flight"""
+    def batch_home_ids(self):
+        """-> (with_batch, late): ids of the batch the last batch_end() handed out that came home in the batch's own launch sequence,
+        and ids mk_sketch_batch_end fetched by its late copy (mk_sketch_batch_home_ids)"""
+        w, l = C.c_uint64(0), C.c_uint64(0)
+        _check(lib.mk_sketch_batch_home_ids(self.h, C.byref(w), C.byref(l)), self.h)
+        return w.value, l.value
+
+    def batch_end(self, views=False):
+        """-> per file (status, alone, [ids per component]) of the oldest batch in flight.  views: the id arrays are the engine's own
+        memory, not copies: valid until the next batch_end() on this engine"""
         if not getattr(self, "_batches", None):  # nothing in flight: let the library say so
             _check(lib.mk_sketch_batch_end(self.h, C.cast((C.c_uint8 * 64)(), C.c_void_p)), self.h)
             raise MkError(MK_ERR_STATE, "mk_sketch_batch_end returned MK_OK without a batch in flight")
@@ -801,7 +811,8 @@ class Engine:
             if out[i].status == MK_OK:
                 for c in range(out[i].r.component_num):
                     comp = out[i].r.components[c]
-                    comps.append(np.ctypeslib.as_array(comp.ids, shape=(comp.n,)).copy() if comp.n else np.zeros(0, np.uint32))
+                    a = np.ctypeslib.as_array(comp.ids, shape=(comp.n,)) if comp.n else np.zeros(0, np.uint32)
+                    comps.append(a if views else a.copy())
             res.append((out[i].status, out[i].alone, comps))
         if isinstance(keep, tuple) and keep[0] == "pinned":
             lib.mk_host_free(keep[2])

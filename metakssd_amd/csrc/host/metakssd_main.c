@@ -278,6 +278,9 @@ static void engine_apply_options(const ctx_t *c, mk_engine *e) {
   /* test hook: MK_BATCH_TAB_BITS=<9..22> gives every file of a batch a table of that size (MK_OPT_BATCH_TAB_BITS), so that files
    * overflow it and take the sketched-alone path of mk_sketch_batch_end */
   if (getenv("MK_BATCH_TAB_BITS")) mk_engine_set_option(e, MK_OPT_BATCH_TAB_BITS, atoi(getenv("MK_BATCH_TAB_BITS")));
+  /* test hook: MK_BATCH_HOME_IDS=<4..> lets at most that many ids come home with a batch (MK_OPT_BATCH_HOME_IDS), so that
+   * mk_sketch_batch_end fetches the rest by its late copy */
+  if (getenv("MK_BATCH_HOME_IDS")) mk_engine_set_option(e, MK_OPT_BATCH_HOME_IDS, atoi(getenv("MK_BATCH_HOME_IDS")));
 }
 
 static mk_engine *engine_get(ctx_t *c) {

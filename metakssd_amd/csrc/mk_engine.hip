@@ -144,6 +144,8 @@ struct mk_engine {
   struct mk_bctx *bctx[3] = {nullptr, nullptr, nullptr};
   uint64_t batch_begun = 0, batch_ended = 0;
   int batch_tb_opt = 0;                /* MK_OPT_BATCH_TAB_BITS: 0 = by the largest file of the batch */
+  uint64_t batch_home_opt = 0;         /* MK_OPT_BATCH_HOME_IDS: 0 = no cap of its own on the ids that come home with a batch */
+  uint64_t home_with_batch = 0, home_late = 0; /* of the batch mk_sketch_batch_end handed out last (mk_sketch_batch_home_ids) */
   std::vector<uint32_t> gz_status;     /* MK_INFL_* per file of the batch mk_sketch_batch_end handed out last (mk_sketch_batch_gz_status) */
   std::vector<uint32_t> gz_pieces;     /* ... and the pieces it was decoded in (mk_sketch_batch_gz_pieces; zeros: not a gunzip batch) */
   const mk_batch_dev *cur_batch = nullptr; /* set around the scan launches of a batch */
@@ -754,6 +756,11 @@ extern "C" int mk_engine_set_option(mk_engine *e, int option, int64_t value) {
       if (value != 0 && (value < 9 || value > 22)) return mk_fail(e, MK_ERR_ARG, "MK_OPT_BATCH_TAB_BITS takes 0 (by file size) or 9..22");
       if (e->batch_begun != e->batch_ended) return mk_fail(e, MK_ERR_STATE, "MK_OPT_BATCH_TAB_BITS while a batch is in flight");
       e->batch_tb_opt = (int)value;
+      return MK_OK;
+    case MK_OPT_BATCH_HOME_IDS:
+      if (value != 0 && (value < 4 || value > ((int64_t)1 << 40))) return mk_fail(e, MK_ERR_ARG, "MK_OPT_BATCH_HOME_IDS takes 0 (the engine's own rule) or at least 4 ids");
+      if (e->batch_begun != e->batch_ended) return mk_fail(e, MK_ERR_STATE, "MK_OPT_BATCH_HOME_IDS while a batch is in flight");
+      e->batch_home_opt = ((uint64_t)value + 3u) & ~(uint64_t)3u;
       return MK_OK;
     case MK_OPT_KEYLIST_CAP: { /* sparse bookkeeping only: the list is grown by the finish / export that needs more */
       if (!e->sparse) return mk_fail(e, MK_ERR_ARG, "MK_OPT_KEYLIST_CAP needs sparse bookkeeping (the dense passes do not grow the key list)");
@@ -2557,11 +2564,14 @@ static int mk_batch_begin_impl(mk_engine *e, int mode, const mk_batch_file *file
    * exactly the ids there are (a copy queued by mk_sketch_batch_end would stand behind the NEXT batch's kernels, and the host would
    * hand every result out one batch late with the device idle meanwhile; a copy COMMAND here would have to guess the count, and be
    * the process's first use of the copy engine where the rows are read in place).  The block holds half of every table, 8 M ids at
-   * most; a batch with more -- none so far -- gets the rest by a copy in mk_sketch_batch_end. */
+   * most; a batch with more gets the rest by a copy in mk_sketch_batch_end: 1 024 files of 9 000 bases at drlevel 0 leave 9.2 M ids,
+   * many small files or a clamped subspace leave more than twice the estimate below (tests/test_gpu_batch_limits.py runs both, and
+   * every boundary of the block through MK_OPT_BATCH_HOME_IDS). */
   /* (twice the ids the batch is expected to leave, not half of every table: pinned memory costs 0.2 ms a MiB to make, and the first three
    * batches of a run each make a block -- 8.4 MB at L2K11, now 4) */
   c->spec_ids = N / 2u < ((uint64_t)8 << 20) ? N / 2u : ((uint64_t)8 << 20);
   { const uint64_t want = (2u * est_ids + 65536u + 3u) & ~(uint64_t)3u; if (want < c->spec_ids) c->spec_ids = want; }
+  if (e->batch_home_opt && e->batch_home_opt < c->spec_ids) c->spec_ids = e->batch_home_opt; /* (a test's cap: never more than the rule gives) */
   if ((rc = mk_pinned_fit(e, (void **)&c->h_ids, &c->h_ids_cap, (size_t)c->spec_ids * 4))) return rc;
   hipLaunchKernelGGL(mk_b_home_kernel, dim3((unsigned)e->num_cu), dim3(256), 0, s, c->hb, (uint4 *)c->h_stat, (uint32_t)(c->stat_bytes / 16u), (uint4 *)c->h_ids,
                      (unsigned long long)c->spec_ids, (const uint32_t *)e->tab.err);
@@ -2623,6 +2633,13 @@ extern "C" int mk_sketch_batch_gz_status(mk_engine *e, uint32_t *status, uint32_
   return MK_OK;
 }
 
+extern "C" int mk_sketch_batch_home_ids(mk_engine *e, uint64_t *with_batch, uint64_t *late) {
+  if (!e) return MK_ERR_ARG;
+  if (with_batch) *with_batch = e->home_with_batch;
+  if (late) *late = e->home_late;
+  return MK_OK;
+}
+
 extern "C" int mk_sketch_batch_end(mk_engine *e, mk_batch_result *out) {
   if (!e || !out) return MK_ERR_ARG;
   if (e->batch_begun == e->batch_ended) return mk_fail(e, MK_ERR_STATE, "mk_sketch_batch_end without a batch in flight");
@@ -2642,6 +2659,8 @@ extern "C" int mk_sketch_batch_end(mk_engine *e, mk_batch_result *out) {
   if (n_out > c->hb.out_cap || misc[0] > c->hb.list_cap) return mk_fail(e, MK_ERR_HIP, "batch: %llu keys, %llu ids for lists of %llu", misc[0], (unsigned long long)n_out, (unsigned long long)c->hb.list_cap);
   int rc = MK_OK;
   const bool more_ids = n_out > c->spec_ids; /* more than came with the batch's own sequence: the rest now */
+  e->home_with_batch = more_ids ? c->spec_ids : n_out;
+  e->home_late = n_out - e->home_with_batch;
   if (more_ids) {
     uint32_t *bigger = nullptr;
     MK_HIP(e, mk_pin_alloc((void **)&bigger, (size_t)n_out * 4 + 4096, hipHostMallocDefault));

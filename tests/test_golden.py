@@ -152,7 +152,8 @@ def test_product_cli_batches_with_files_that_cannot_travel_in_one(shuf, flags, s
     with batches of two files and of 1 MiB; with files that GREW or SHRANK between the planning stat() and the readers' pread()
     (MK_TEST_PLAN_SKEW: a grown file is sketched alone from all of its text, a shrunk one is what it is now -- both read to EOF like
     the reference's zcat -fc | fread, iseq2comem.c:226-233); and with 512-slot tables per file (MK_BATCH_TAB_BITS=9), which send most
-    files to the sketched-alone path of mk_sketch_batch_end while the next batch is queued"""
+    files to the sketched-alone path of mk_sketch_batch_end while the next batch is queued; and with a pinned block of 64 or 4 ids per
+    batch (MK_BATCH_HOME_IDS), so that mk_sketch_batch_end fetches the rest of a batch's ids by its late copy, behind the next batch"""
     import gzip
     import numpy as np
     import util_inputs as ui
@@ -179,7 +180,9 @@ def test_product_cli_batches_with_files_that_cannot_travel_in_one(shuf, flags, s
                 ("text", ["--batch-text"], {}), ("narrow", ["--batch-narrow"], {}),
                 ("grew", ["--batch-files", "3"], {"MK_TEST_PLAN_SKEW": "2:-301"}), ("grew_text", ["--batch-text"], {"MK_TEST_PLAN_SKEW": "3:-17"}),
                 ("shrank", [], {"MK_TEST_PLAN_SKEW": "2:4099"}), ("shrank_text", ["--batch-text", "--batch-files", "4"], {"MK_TEST_PLAN_SKEW": "3:1000"}),
-                ("tiny_tables", ["--batch-files", "3"], {"MK_BATCH_TAB_BITS": "9"}), ("tiny_tables_text", ["--batch-text", "--batch-files", "4"], {"MK_BATCH_TAB_BITS": "9"}))
+                ("tiny_tables", ["--batch-files", "3"], {"MK_BATCH_TAB_BITS": "9"}), ("tiny_tables_text", ["--batch-text", "--batch-files", "4"], {"MK_BATCH_TAB_BITS": "9"}),
+                ("late_ids", ["--batch-files", "3"], {"MK_BATCH_HOME_IDS": "64"}), ("late_ids_text", ["--batch-text", "--batch-files", "4"], {"MK_BATCH_HOME_IDS": "4"}),
+                ("late_ids_tiny_tables", ["--batch-files", "3"], {"MK_BATCH_HOME_IDS": "64", "MK_BATCH_TAB_BITS": "9"}))
     for tag, extra, env in variants:
         out = str(tmp_path / tag)
         r = subprocess.run(base + extra + ["-o", out, str(d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, **env))
