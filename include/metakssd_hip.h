@@ -892,7 +892,8 @@ int mk_sketch_batch_gz_status(mk_engine *e, uint32_t *status, uint32_t nfiles);
  * pieces, the markers are replaced, and the CRC32 and the length of the text are held against the trailer.
  *   mk_gzip_scan_stream   host: header and trailer of a single-member gzip file of any size
  *   mk_inflate_stream     device: everything up to the checked text, with a copy back (tests, tools)
- *   mk_sketch_push_gzip   the same bound to an engine: the text is framed and scanned like mk_sketch_push_bgzf's */
+ *   mk_sketch_push_gzip   the same bound to an engine: the text is framed and scanned like mk_sketch_push_bgzf's
+ *   mk_sketch_push_gzip_q ... and like mk_sketch_push_bgzf_q's, for the -n / -Q reader */
 #define MK_INFL_MISSED 9    /* a piece decoded past the start of the next one: the finder's candidate was no block start */
 #define MK_INFL_CAPACITY 10 /* a piece gave more than R times the compressed bytes it covers */
 /* eleven: (MK_GUNZIP_MEMBERS) behind a member's trailer and in front of the payload's end the bytes are not a gzip header with at
@@ -959,6 +960,14 @@ typedef struct mk_gunzip_stats {
  * is checked last, so a status may appear AFTER rows were pushed: the caller finishes and drops the sketch, begins it anew and
  * reads the file another way.  Engines with MK_OPT_SPLIT_CUS: MK_ERR_STATE.  Error text: mk_bgzf_last_error. */
 int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, uint64_t first_ordinal, mk_gunzip_stats *st);
+/* The same for a sketch begun with mk_sketch_begin_occ (the -n / -Q reader, fastq2co).  The text is made exactly as
+ * mk_sketch_push_gzip makes it: geometry, statuses, the CRC and length check and MK_GUNZIP_MEMBERS are unchanged.  Rows and errors
+ * are those of mk_fastq_frame_q over the whole text with final != 0 and records_before = 0: one row per record whose four lines
+ * are terminated, and the first record of a file without a complete one; bases whose quality byte is below qmin become 'N' as in
+ * mk_sketch_push_bgzf_q.  MK_ERR_FORMAT with st->bad_status == 0: a line of 4095+ characters, or more than MK_FQ_CARRY (16 KiB)
+ * bytes behind a slice's last complete record; the caller begins the sketch anew.  The framing keeps 8 bytes per record a slice of
+ * 128 MiB can hold: 256 MiB for a full slice. */
+int mk_sketch_push_gzip_q(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int32_t qmin, uint64_t first_ordinal, mk_gunzip_stats *st);
 
 /* ---- a BATCH of single-member gzip genome files, many wavefronts per file ----------------------------------------
  * mk_sketch_batch_begin_gz with the decode above in place of one wavefront per file: a wave per span of S compressed bytes finds

@@ -199,6 +199,7 @@ def _load():
                               C.POINTER(GunzipPiecesC)],
         "mk_inflate_stream_members": [vp, C.POINTER(u64)],
         "mk_sketch_push_gzip": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), u64, C.POINTER(GunzipStatsC)],
+        "mk_sketch_push_gzip_q": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), i32, u64, C.POINTER(GunzipStatsC)],
         "mk_inflate_members": [vp, vp, C.c_size_t, C.POINTER(GzMemberC), u32, vp, C.c_size_t, C.POINTER(GzMemberResultC)],
         "mk_sketch_finish": [vp, C.POINTER(ResultC)],
         "mk_sketch_finish_begin": [vp],
@@ -598,13 +599,16 @@ class Engine:
             raise err
         return st
 
-    def push_gzip(self, path, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0, members=False):
+    def push_gzip(self, path, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0, members=False, qmin=None):
         """a single-member gzip FASTQ file into the sketch in progress (mk_sketch_push_gzip) -> GunzipStatsC; an inflate status or
         a long line raises MkError(MK_ERR_FORMAT) with the statistics in .stats: the sketch is then to be begun anew"""
         o, st = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), GunzipStatsC()
         fd = os.open(path, os.O_RDONLY)
         try:
-            rc = lib.mk_sketch_push_gzip(self.h, fd, os.fstat(fd).st_size, C.byref(o), first_ordinal, C.byref(st))
+            if qmin is None:
+                rc = lib.mk_sketch_push_gzip(self.h, fd, os.fstat(fd).st_size, C.byref(o), first_ordinal, C.byref(st))
+            else:
+                rc = lib.mk_sketch_push_gzip_q(self.h, fd, os.fstat(fd).st_size, C.byref(o), qmin, first_ordinal, C.byref(st))
         finally:
             os.close(fd)
         if rc:
@@ -612,6 +616,10 @@ class Engine:
             err.stats = st
             raise err
         return st
+
+    def push_gzip_q(self, path, qmin=0, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0, members=False):
+        """the same for a sketch begun with begin_occ (mk_sketch_push_gzip_q): fastq2co's record rule and its -Q mask"""
+        return self.push_gzip(path, span_bytes, ratio, batch_spans, first_ordinal, members, qmin=qmin)
 
     def push_bgzf_q(self, path, qmin=0, chunk_bytes=0, first_ordinal=0):
         """the same for a sketch begun with begin_occ (mk_sketch_push_bgzf_q): fastq2co's record rule and its -Q mask"""

@@ -96,8 +96,8 @@ typedef struct {
                             * children are 6-14 times faster on 1 024 genomes */
   int device_inflate_q;    /* --device-inflate: a BGZF-compressed FASTQ on the -n / -Q reader (dist without -A) is inflated, framed and quality-masked on
                             * the device (mk_sketch_push_bgzf_q), 11-12 times the zcat pipe on 2 M reads.  Opt-in: without the switch this input keeps zcat */
-  int device_gunzip;       /* --device-gunzip: an ordinary single-member .gz FASTQ on the -A reader is inflated by many wavefronts (mk_sketch_push_gzip,
-                            * DESIGN.md 4.14).  Opt-in: without the switch such a file keeps zcat */
+  int device_gunzip;       /* --device-gunzip: an ordinary single-member .gz FASTQ is inflated by many wavefronts, on the -A reader (mk_sketch_push_gzip,
+                            * DESIGN.md 4.14) and on the -n / -Q reader (mk_sketch_push_gzip_q).  Opt-in: without the switch such a file keeps zcat */
   int gz_gunzip;           /* --device-gunzip on a directory of genomes: the gz batches are inflated by many wavefronts per file
                             * (mk_sketch_batch_begin_gunzip); decides the genome route when --device-inflate is given too */
   mk_gunzip_opts gunzip_opts;   /* --gunzip-span-bytes, --gunzip-ratio, --gunzip-batch-spans (test hooks; 0 = the library's defaults) */

@@ -521,11 +521,12 @@ static int sketch_fastq_bgzf(ctx_t *c, const char *path) {
   return 1;
 }
 /* --device-gunzip: a .gz that is ONE gzip member (mk_gzip_scan_stream; a BGZF file has gone its own way before) is inflated, checked
- * and framed on the device.  0: not such a file, or the device route gave it up with a status -- then what was pushed is finished
- * and dropped, the caller begins the sketch anew and reads the file from its start through `zcat -fc`, which alone decides whether
- * the file is damaged; --timing says so ("fallback": the status). */
+ * and framed on the device, for the -A reader and for the -n / -Q reader (c->occ: mk_sketch_push_gzip_q with c->qmin).  0: not such
+ * a file, or the device route gave it up with a status or a line of 4095+ characters -- then what was pushed is finished and
+ * dropped, the caller begins the sketch anew and reads the file from its start through `zcat -fc`, which alone decides whether
+ * the file is damaged; --timing says so ("fallback": the status, or "long line"). */
 static int sketch_fastq_gunzip(ctx_t *c, const char *path) {
-  if (!g_opt.device_gunzip || !c->bgzf_ok || c->occ || g_opt.no_device_inflate || !has_suffix(path, ".gz")) return 0;
+  if (!g_opt.device_gunzip || !c->bgzf_ok || g_opt.no_device_inflate || !has_suffix(path, ".gz")) return 0;
   const int fd = open(path, O_RDONLY);
   if (fd < 0) return 0;
   struct stat st;
@@ -534,7 +535,8 @@ static int sketch_fastq_gunzip(ctx_t *c, const char *path) {
   mk_engine *e = sketch_engine(c);
   if (c->t_first_push == 0) c->t_first_push = now_s() - g_t0;
   mk_gunzip_stats gs;
-  const int rc = mk_sketch_push_gzip(e, fd, (size_t)st.st_size, &g_opt.gunzip_opts, c->next_ordinal, &gs);
+  const int rc = c->occ ? mk_sketch_push_gzip_q(e, fd, (size_t)st.st_size, &g_opt.gunzip_opts, c->qmin, c->next_ordinal, &gs)
+                        : mk_sketch_push_gzip(e, fd, (size_t)st.st_size, &g_opt.gunzip_opts, c->next_ordinal, &gs);
   close(fd);
   if (rc == MK_ERR_FORMAT) {
     mk_result dropped;
@@ -545,7 +547,7 @@ static int sketch_fastq_gunzip(ctx_t *c, const char *path) {
     g_gz_fallback = gs.bad_status ? mk_gunzip_status_text(gs.bad_status) : "long line";
     return 0;
   }
-  if (rc != MK_OK) die("mk_sketch_push_gzip failed (%d): %s", rc, mk_bgzf_last_error());
+  if (rc != MK_OK) die("%s failed (%d): %s", c->occ ? "mk_sketch_push_gzip_q" : "mk_sketch_push_gzip", rc, mk_bgzf_last_error());
   c->next_ordinal += gs.rows;
   c->nrows_total += gs.rows;
   c->t_last_push = now_s() - g_t0;

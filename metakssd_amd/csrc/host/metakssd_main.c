@@ -97,7 +97,7 @@ static void parse_dist_options(int argc, char **argv) {
     /* --device-inflate: the two opt-in device routes -- single-member .gz genomes in gz batches and a BGZF FASTQ on
      * the -n / -Q reader (4.12); the -A reader's BGZF route needs no switch.  The later of the two switches holds. */
     else if (!strcmp(argv[i], "--device-inflate")) { o->no_device_inflate = 0; o->gz_batches = 1; o->device_inflate_q = 1; }
-    else if (!strcmp(argv[i], "--device-gunzip")) o->device_gunzip = 1; /* dist -A: a single-member .gz FASTQ inflated on the device */
+    else if (!strcmp(argv[i], "--device-gunzip")) o->device_gunzip = 1; /* dist -A and dist -n / -Q: a single-member .gz FASTQ inflated on the device */
     else if (!strcmp(argv[i], "--gunzip-members")) o->gunzip_opts.flags |= MK_GUNZIP_MEMBERS; /* ... and a concatenation of members */
     else if (!strcmp(argv[i], "--gunzip-span-bytes") && more) o->gunzip_opts.span_bytes = (uint32_t)atoll(argv[++i]);
     else if (!strcmp(argv[i], "--gunzip-ratio") && more) o->gunzip_opts.ratio = (uint32_t)atoll(argv[++i]);

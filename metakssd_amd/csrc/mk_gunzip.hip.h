@@ -837,7 +837,11 @@ extern "C" int mk_inflate_stream_members(mk_inflate *h, uint64_t *members) {
   return MK_OK;
 }
 
-extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, uint64_t first_ordinal, mk_gunzip_stats *st) {
+/* both readers' route: occ == false is mk_fastq_frame's rule (-A), occ == true mk_fastq_frame_q's (quality mask qmin), one row a
+ * record.  What the second adds to the sink: d_qinfo, two words per record a slice can hold; the file's record count (stats.rows),
+ * which decides the first-record exception -- it can only arise in the last slice of the last batch, whose text [t0, e1) is then the
+ * whole file: everything in front of it went through the carry, possibly in front of an empty batch. */
+static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, bool occ, int32_t qmin, uint64_t first_ordinal, mk_gunzip_stats *st) {
   if (!e || fd < 0) return MK_ERR_ARG;
   mk_gunzip_stats stats;
   memset(&stats, 0, sizeof stats);
@@ -854,12 +858,12 @@ extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_g
   if (rc) return rc;
   struct frame_bufs { /* the framing's own buffers */
     uint8_t *d_rows = nullptr, *d_carry = nullptr;
-    uint32_t *d_tile_cnt = nullptr, *d_tile_last = nullptr;
+    uint32_t *d_tile_cnt = nullptr, *d_tile_last = nullptr, *d_qinfo = nullptr;
     mk_fq_res *d_res = nullptr, *h_res = nullptr;
-    uint64_t rows_cap = 0;
+    uint64_t rows_cap = 0, qinfo_cap = 0; /* bytes, words */
     hipEvent_t ev[2] = {nullptr, nullptr};
     ~frame_bufs() {
-      (void)hipFree(d_rows); (void)hipFree(d_carry); (void)hipFree(d_tile_cnt); (void)hipFree(d_tile_last); (void)hipFree(d_res);
+      (void)hipFree(d_rows); (void)hipFree(d_carry); (void)hipFree(d_tile_cnt); (void)hipFree(d_tile_last); (void)hipFree(d_qinfo); (void)hipFree(d_res);
       if (h_res) (void)hipHostFree(h_res);
       for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
     }
@@ -889,14 +893,22 @@ extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_g
   };
   auto sink = [&](uint8_t *d_text, uint64_t n, bool final_batch) -> int {
     if (n == 0 && !final_batch) return MK_OK;
-    { /* rows of one slice at most (a row is a line of the text, padded) */
+    const uint32_t qcap = mk_fq_qcap(MK_FQ_CARRY + std::min<uint64_t>(n, MK_GUN_SLICE)); /* records a slice with its carry can hold */
+    { /* rows of one slice at most (a row is a line of the text, padded); occ: two words per possible record of a slice */
       const uint64_t need = std::max<uint64_t>(std::min<uint64_t>(n, MK_GUN_SLICE) + MK_FQ_CARRY, (uint64_t)8 << 20) + 4096u;
+      const uint64_t qneed = occ ? 2u * (uint64_t)qcap : 0u;
+      if (need > F.rows_cap || qneed > F.qinfo_cap) MK_GUN_HIP(hipStreamSynchronize(S));
       if (need > F.rows_cap) {
-        MK_GUN_HIP(hipStreamSynchronize(S));
         (void)hipFree(F.d_rows);
         F.d_rows = nullptr; F.rows_cap = 0;
         MK_GUN_HIP(mk_dev_alloc(&F.d_rows, need));
         F.rows_cap = need;
+      }
+      if (qneed > F.qinfo_cap) {
+        (void)hipFree(F.d_qinfo);
+        F.d_qinfo = nullptr; F.qinfo_cap = 0;
+        MK_GUN_HIP(mk_dev_alloc(&F.d_qinfo, qneed * sizeof(uint32_t)));
+        F.qinfo_cap = qneed;
       }
     }
     if (carry) {
@@ -910,19 +922,34 @@ extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_g
       uint8_t *base = d_text + off;
       const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + sl, nn = e1 - t0;
       MK_GUN_HIP(hipEventRecord(F.ev[0], S));
-      MK_GUN_HIP(mk_launch_frame_count(S, base, t0, e1, final, F.d_tile_cnt, F.d_tile_last, nullptr, 0, F.d_res));
+      if (occ) MK_GUN_HIP(mk_launch_frame_count_q(S, base, t0, e1, final, F.d_tile_cnt, F.d_tile_last, nullptr, 0, F.d_res, F.d_qinfo, qcap));
+      else MK_GUN_HIP(mk_launch_frame_count(S, base, t0, e1, final, F.d_tile_cnt, F.d_tile_last, nullptr, 0, F.d_res));
       MK_GUN_HIP(hipEventRecord(F.ev[1], S));
       MK_GUN_HIP(hipMemcpyAsync(F.h_res, F.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
       MK_GUN_HIP(hipStreamSynchronize(S));
-      const mk_fq_res r = *F.h_res;
+      mk_fq_res r = *F.h_res;
+      const bool first = occ && mk_fq_res_q(r, nn, final, stats.rows);
       float ms = 0.f;
       MK_GUN_HIP(hipEventElapsedTime(&ms, F.ev[0], F.ev[1]));
       stats.frame_ms += ms;
       if (r.maxline >= MK_FQ_LINE_MAX || (!final && nn - r.consumed > MK_FQ_CARRY)) { long_line = true; return MK_ERR_FORMAT; }
+      if (first) { /* no complete record in the whole file: its first one is walked all the same, if it has a sequence line */
+        hipLaunchKernelGGL(mk_fq_first_q_kernel, dim3(1), dim3(64), 0, S, (const uint8_t *)base, t0, e1, qmin, F.d_res, F.d_rows);
+        MK_GUN_HIP(hipGetLastError());
+        MK_GUN_HIP(hipMemcpyAsync(F.h_res, F.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
+        MK_GUN_HIP(hipStreamSynchronize(S));
+        if (F.h_res->nrec) {
+          const int prc = mk_sketch_push_reads_device(e, F.d_rows, mk_fq_stride(F.h_res->maxseq), 1, ordinal);
+          if (prc) { snprintf(R.err, sizeof R.err, "%s", mk_last_error(e)); return prc; }
+          ordinal++;
+          stats.rows++;
+        }
+      }
       const uint32_t stride = mk_fq_stride(r.maxseq), per = (uint32_t)(F.rows_cap / stride);
       for (uint32_t r0 = 0; r0 < r.nrec; r0 += per) {
         const uint32_t r1 = r.nrec - r0 < per ? r.nrec : r0 + per;
-        MK_GUN_HIP(mk_launch_frame_rows(S, base, t0, e1, F.d_tile_cnt, r0, r1, stride, F.d_rows));
+        if (occ) MK_GUN_HIP(mk_launch_frame_rows_q(S, base, t0, e1, F.d_tile_cnt, r0, r1, stride, F.d_qinfo, qmin, F.d_rows));
+        else MK_GUN_HIP(mk_launch_frame_rows(S, base, t0, e1, F.d_tile_cnt, r0, r1, stride, F.d_rows));
         const int prc = mk_sketch_push_reads_device(e, F.d_rows, stride, r1 - r0, ordinal);
         if (prc) { snprintf(R.err, sizeof R.err, "%s", mk_last_error(e)); return prc; }
         ordinal += r1 - r0;
@@ -952,4 +979,12 @@ extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_g
     return MK_ERR_FORMAT;
   }
   return MK_OK;
+}
+
+extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, uint64_t first_ordinal, mk_gunzip_stats *st) {
+  return mk_push_gzip(e, fd, size, opts, false, 0, first_ordinal, st);
+}
+
+extern "C" int mk_sketch_push_gzip_q(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int32_t qmin, uint64_t first_ordinal, mk_gunzip_stats *st) {
+  return mk_push_gzip(e, fd, size, opts, true, qmin, first_ordinal, st);
 }

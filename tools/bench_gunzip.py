@@ -12,7 +12,11 @@ file, and mk_inflate_stream's piece table gives the largest text-to-compressed r
 --members N[,N...]: the same reads as a CONCATENATION of N equal members (cut at byte offsets, so records straddle the boundaries), per
 level and N: `--device-gunzip --gunzip-members`, the run without switches and, with --parent-cli, that binary with
 `--device-gunzip` (which falls back to zcat for more than one member), taking turns; with --rocprof one more run per file under
-`rocprofv3 --kernel-trace --stats`, whose kernel totals go into the JSON line and, as CSV, into that directory."""
+`rocprofv3 --kernel-trace --stats`, whose kernel totals go into the JSON line and, as CSV, into that directory.
+
+--reader nQ: the same legs through the other FASTQ reader, `dist -L L3K11.shuf -n 2 -Q 53` (fastq2co's record rule and quality mask,
+mk_sketch_push_gzip_q), for the one-member form and for --members.  --parent-switch: the parent's binary gets
+`--device-gunzip` too (the shared sink must cost the -A route nothing).  --span-runs 0 leaves out the span sweep and the piece ratios."""
 import argparse
 import filecmp
 import json
@@ -34,6 +38,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 CLI = os.path.join(ROOT, "metakssd_amd", "bin", "metakssd")
 SEED, READ_LEN = 20261002, 150  # bench.py's SEED and READ_LEN
 SPANS = (128 << 10, 256 << 10, 512 << 10, 1 << 20)
+READERS = {"A": ["-A"], "nQ": ["-n", "2", "-Q", "53"]}
+READER = READERS["A"]  # --reader
 
 
 def compress(args):
@@ -113,8 +119,8 @@ def bench_members(a, tmp, shuf, fq, levels, out):
                     e["speedup_vs_parent"] = round(statistics.median(par) / statistics.median(dev), 2)
                 if a.rocprof:
                     os.makedirs(a.rocprof, exist_ok=True)
-                    name = "gunzip_members_l%d_m%d" % (lv, n)
-                    subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", a.rocprof, "-o", name, "--", CLI, "dist", "-L", shuf, "-A",
+                    name = "gunzip_members_%sl%d_m%d" % ("" if a.reader == "A" else a.reader + "_", lv, n)
+                    subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", a.rocprof, "-o", name, "--", CLI, "dist", "-L", shuf] + READER + [
                                     "-o", os.path.join(tmp, "prof"), "--quiet", "--slow-exit", "--device-gunzip", "--gunzip-members", gz],
                                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
                     e["rocprof_kernel_totals_ms"] = kernel_totals(a.rocprof, name)
@@ -125,12 +131,18 @@ def bench_members(a, tmp, shuf, fq, levels, out):
 def run_cli(cli, shuf, out, inp, extra):
     shutil.rmtree(out, ignore_errors=True)
     t0 = time.perf_counter()
-    r = subprocess.run([cli, "dist", "-L", shuf, "-A", "-o", out, "--quiet", "--timing"] + extra + [inp], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=3000)
+    r = subprocess.run([cli, "dist", "-L", shuf] + READER + ["-o", out, "--quiet", "--timing"] + extra + [inp], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=3000)
     dt = time.perf_counter() - t0
     if r.returncode != 0:
         raise RuntimeError(r.stderr.decode(errors="replace")[-500:])
     route = [json.loads(ln) for ln in r.stdout.decode().splitlines() if ln.startswith('{"input"')]
     return dt, route[0] if route else None
+
+
+def zcat_alone(gz):
+    t0 = time.perf_counter()
+    subprocess.run(["zcat", "-fc", "--", gz], stdout=subprocess.DEVNULL, check=True)
+    return time.perf_counter() - t0
 
 
 def same(a, b):
@@ -151,16 +163,20 @@ def main():
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--parent-cli", default=None, help="a metakssd binary built from the parent commit: its default route is timed too")
     ap.add_argument("--members", default=None, help="N[,N...]: the reads as N equal gzip members; times the --gunzip-members route instead of the one-member legs")
+    ap.add_argument("--reader", choices=sorted(READERS), default="A", help="A: dist -A (the counted sketch); nQ: dist -n 2 -Q 53 (fastq2co's reader)")
+    ap.add_argument("--parent-switch", action="store_true", help="the parent's binary runs with --device-gunzip too, not on its default route")
     ap.add_argument("--rocprof", default=None, help="directory: one more device-route run per level under `rocprofv3 --kernel-trace --stats`")
     a = ap.parse_args()
+    global READER
+    READER = READERS[a.reader]
     from golden_cases import make_shuf
     from metakssd_amd import capi
     if capi.device_count() < 1:
         sys.exit("bench_gunzip: no HIP device")
     tmp = tempfile.mkdtemp(prefix="mkgunzip_", dir=a.workdir or ("/dev/shm" if os.path.isdir("/dev/shm") else None))
     levels = [int(x) for x in a.levels.split(",")]
-    out = {"what": "`metakssd dist -L L3K11.shuf -A` on %d reads of %d bases as ONE gzip member, median of %d runs from process start to the "
-                   "directory on disk, legs taking turns" % (a.reads, READ_LEN, a.runs), "reads": a.reads, "levels": {}}
+    out = {"what": "`metakssd dist -L L3K11.shuf %s` on %d reads of %d bases as ONE gzip member, median of %d runs from process start to the "
+                   "directory on disk, legs taking turns" % (" ".join(READER), a.reads, READ_LEN, a.runs), "reader": a.reader, "reads": a.reads, "levels": {}}
     try:
         shuf = os.path.join(tmp, "L3K11.shuf")
         make_shuf("L3K11", shuf)
@@ -179,6 +195,7 @@ def main():
         t_plain = statistics.median(run_cli(CLI, shuf, d_plain, fq, [])[0] for _ in range(3))
         out["plain_fastq"] = {"wall_s": round(t_plain, 4), "gbases_s": round(bases / t_plain / 1e9, 3)}
         gb = lambda t: round(bases / t / 1e9, 3)
+        prof = {}
         for lv in levels:
             print("bench_gunzip: level %d, %d bytes" % (lv, comps[lv]), file=sys.stderr, flush=True)
             gz = gzs[lv]
@@ -191,28 +208,39 @@ def main():
                 dt, route = run_cli(CLI, shuf, d_zc, gz, [])
                 assert route and route["route"] == "zcat" and "fallback" not in route, route
                 zc.append(dt)
-                if a.parent_cli:
+                if a.parent_cli and a.parent_switch:
+                    # a device-route process right behind another GPU process takes 0.2 s longer from start to exit than one behind
+                    # two seconds of `zcat` alone (profiles/r16_gunzip_q_bench.json): both binaries' device legs follow such a leg
+                    zo.append(zcat_alone(gz))
+                    par.append(run_cli(a.parent_cli, shuf, os.path.join(tmp, "par"), gz, ["--device-gunzip"])[0])
+                elif a.parent_cli:
                     par.append(run_cli(a.parent_cli, shuf, os.path.join(tmp, "par"), gz, [])[0])
-                t0 = time.perf_counter()
-                subprocess.run(["zcat", "-fc", "--", gz], stdout=subprocess.DEVNULL, check=True)
-                zo.append(time.perf_counter() - t0)
+                zo.append(zcat_alone(gz))
             if a.rocprof:
                 os.makedirs(a.rocprof, exist_ok=True)
-                subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", a.rocprof, "-o", "gunzip_l%d" % lv, "--", CLI, "dist", "-L", shuf, "-A", "-o",
+                name = "gunzip_%sl%d" % ("" if a.reader == "A" else a.reader + "_", lv)
+                subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", a.rocprof, "-o", name, "--", CLI, "dist", "-L", shuf] + READER + ["-o",
                                 os.path.join(tmp, "prof"), "--quiet", "--slow-exit", "--device-gunzip", gz], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+                prof[lv] = kernel_totals(a.rocprof, name)
             k = {f: med([r[f] for r in routes]) for f in ("find_ms", "decode_ms", "resolve_ms", "frame_ms", "read_s", "route_total_s")}
             out["levels"][str(lv)] = {
                 "comp_bytes": comps[lv], "ratio": round(text_bytes / comps[lv], 3), "pieces": routes[0]["pieces"], "batches": routes[0]["batches"],
                 "device_gunzip": {"wall_s": med(dev), "gbases_s": gb(statistics.median(dev)), "runs_s": [round(x, 4) for x in dev]},
                 "zcat_route": {"wall_s": med(zc), "gbases_s": gb(statistics.median(zc)), "runs_s": [round(x, 4) for x in zc]},
-                "parent_zcat_route": {"wall_s": med(par), "gbases_s": gb(statistics.median(par))} if par else None,
+                "parent_device_gunzip" if a.parent_switch else "parent_zcat_route":
+                    {"wall_s": med(par), "gbases_s": gb(statistics.median(par)), "runs_s": [round(x, 4) for x in par]} if par else None,
                 "zcat_alone": {"wall_s": med(zo), "gbases_s": gb(statistics.median(zo))},
                 "speedup_vs_zcat_route": round(statistics.median(zc) / statistics.median(dev), 2),
                 "speedup_vs_parent": round(statistics.median(par) / statistics.median(dev), 2) if par else None,
                 "kernels_ms": k,
+                "rocprof_kernel_totals_ms": prof.get(lv),
                 "decode_text_gb_s": round(text_bytes / k["decode_ms"] / 1e6, 2),
-                "sketch_dirs_equal": bool(same(d_dev, d_zc)),
+                "sketch_dirs_equal": bool(same(d_dev, d_zc) and (not par or same(d_dev, os.path.join(tmp, "par")))),
             }
+        if a.span_runs <= 0:
+            out["ok"] = all(v["sketch_dirs_equal"] for v in out["levels"].values())
+            print(json.dumps(out))
+            return 0 if out["ok"] else 1
         # the span size, on the last level's file
         gz, sweep = gzs[levels[-1]], {}
         for S in SPANS:
