@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tools/fuzz_parity.py -- randomized differential test of the HIP engine against the CPU oracle (GPU box only).
 
-    python tools/fuzz_parity.py [--cases 200] [--seed 1]
+    python tools/fuzz_parity.py [--cases 200] [--seed 1] [--geom k,subk,drlevel ...]
 
 Every case draws a .shuf geometry, a sketch flavour (-A counted / FASTA set / FASTA -u / FASTQ occurrence set), a row stride,
 (half of the -A cases: the sketch merged from 2 / 3 / 5 shards through the multi-GPU ABI, by the gather or by key slices,)
@@ -64,6 +64,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--start", type=int, default=0, help="first case (every case draws from its own stream: --start N --cases 1 replays case N)")
     ap.add_argument("--trace", action="store_true", help="print every case's number before it runs and its description behind it")
+    ap.add_argument("--geom", action="append", default=[], metavar="k,subk,drlevel",
+                    help="draw the geometries from these instead of the built-in list (repeatable; e.g. --geom 13,6,5 --geom 12,4,4 for wide k-mers)")
     ap.add_argument("--big", action="store_true", help="also draw the 16-component L2K11 geometry (slow oracle)")
     ap.add_argument("--big-rate", type=float, default=0.08, help="share of the cases that draw it (with --big)")
     ap.add_argument("--sparse", type=int, default=-1, help="MK_OPT_SPARSE: -1 by table size, 0 off, 1 on")
@@ -81,6 +83,9 @@ def main():
         def _begin(self, mode=capi.MK_MODE_KOC):
             return _begin0(self, mode | (capi.MK_BEGIN_NOTHING_FOLLOWS if trs.rand() < a.tail_rate else 0))
         capi.Engine.begin = _begin
+    geoms = [tuple(int(x) for x in g.split(",")) for g in a.geom] or GEOM
+    if any(len(g) != 3 for g in geoms):
+        ap.error("--geom takes k,subk,drlevel")
     engines, oracles, shufs = {}, {}, {}
     bad = 0
     nonempty = total_ids = crowded = 0
@@ -88,7 +93,7 @@ def main():
         if a.trace:
             print("case", case, flush=True)
         rs = np.random.RandomState(a.seed * 100003 + case)
-        k, subk, drl = GEOM_BIG if (a.big and rs.rand() < a.big_rate) else GEOM[rs.randint(0, len(GEOM))]
+        k, subk, drl = GEOM_BIG if (a.big and rs.rand() < a.big_rate) else geoms[rs.randint(0, len(geoms))]
         key = (k, subk, drl)
         if key not in shufs:
             shufs[key] = capi.Shuf.generate(k, subk, drl, 1000 + k * 100 + subk * 10 + drl)
