@@ -276,6 +276,15 @@ int mk_sketch_finish(mk_engine *e, mk_result *out);
  * _begin. */
 int mk_sketch_finish_begin(mk_engine *e);
 int mk_sketch_finish_end(mk_engine *e, mk_result *out);
+/* The finish that ends at the key list, for callers that need the sketch as a multiset and stay on the device
+ * (mk_composite_query_sample_keys): the compaction only -- no priority layout, no dump, no copy of ids to the host.  *keys_dev /
+ * *counts_dev are the engine's list of the *n distinct keys and min(count, 65535): component = key % component_num, id = key >>
+ * comp_code_bits; as a multiset of (component, id, count) exactly what mk_sketch_finish would hand out (key 0 included when it has a
+ * count), in no particular order.  The sketch is over as after mk_sketch_finish and the same status comes back for the same pushes
+ * (MK_ERR_CROWDED, MK_ERR_FORMAT); device time goes to mk_profile::finish_ms.  The arrays are device memory, valid until the next call
+ * on the engine that begins or finishes a sketch.  MK_MODE_KOC only: the other modes decide in the dump which keys are written
+ * (MK_ERR_ARG, the sketch stays open). */
+int mk_sketch_finish_keys(mk_engine *e, const uint64_t **keys_dev, const uint32_t **counts_dev, uint64_t *n);
 int mk_result_release(mk_engine *e, mk_result *r);
 int mk_engine_sync(mk_engine *e);
 
@@ -678,6 +687,15 @@ int mk_composite_load_component(mk_composite *h, uint32_t c, const uint32_t *ref
 int mk_composite_query_begin(mk_composite *h, uint32_t nsamples);
 int mk_composite_query_component(mk_composite *h, uint32_t c, const uint32_t *ids, const uint16_t *counts, const uint64_t *index);
 int mk_composite_query_finish(mk_composite *h, const mk_composite_row **rows, uint64_t *row_end /* [nsamples] */);
+/* A sample that arrives as a device key list (mk_sketch_finish_keys): n DISTINCT keys with their counts, in any order,
+ * on the handle's device.  Component = key % comp_num, id = key >> comp_code_bits, count clamped to 65535.  Samples come in ascending
+ * order, k = 0, 1, ... (MK_ERR_ARG otherwise, and for a comp_code_bits with 1 << comp_code_bits != the loaded comp_num, and for more
+ * than 16 components); a batch may be finished before all of its nsamples have come: the missing ones are empty.  A batch takes its
+ * samples either by mk_composite_query_component or by this call (MK_ERR_STATE for a mix).  When the call returns the list has been
+ * read: the caller may reuse it.  Because the keys of a sample are distinct no id repeats within a sample, and such a batch needs no
+ * (sample, id) table: every position with a row counts. */
+int mk_composite_query_sample_keys(mk_composite *h, uint32_t k, const uint64_t *keys_dev, const uint32_t *counts_dev, uint64_t n,
+                                   uint32_t comp_code_bits);
 enum { MK_COMPOSITE_OPT_MAX_HITS = 1 }; /* hit-buffer capacity in hits (tests: forces the splitting at small sizes) */
 int mk_composite_set_option(mk_composite *h, int option, int64_t value);
 /* measurement: device time of the load kernels since load_begin and of the query kernels since query_begin (HIP events on the handle's

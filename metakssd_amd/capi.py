@@ -202,6 +202,7 @@ def _load():
         "mk_sketch_push_gzip_q": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), i32, u64, C.POINTER(GunzipStatsC)],
         "mk_inflate_members": [vp, vp, C.c_size_t, C.POINTER(GzMemberC), u32, vp, C.c_size_t, C.POINTER(GzMemberResultC)],
         "mk_sketch_finish": [vp, C.POINTER(ResultC)],
+        "mk_sketch_finish_keys": [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)],
         "mk_sketch_finish_begin": [vp],
         "mk_sketch_finish_end": [vp, C.POINTER(ResultC)],
         "mk_result_release": [vp, C.POINTER(ResultC)],
@@ -269,6 +270,7 @@ def _load():
         "mk_composite_load_component": [vp, u32, vp, vp],
         "mk_composite_query_begin": [vp, u32],
         "mk_composite_query_component": [vp, u32, vp, vp, vp],
+        "mk_composite_query_sample_keys": [vp, u32, vp, vp, u64, u32],
         "mk_composite_query_finish": [vp, C.POINTER(vp), vp],
         "mk_composite_set_option": [vp, C.c_int, C.c_int64],
         "mk_composite_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
@@ -688,6 +690,13 @@ class Engine:
         self.last_total = r.total
         lib.mk_result_release(self.h, C.byref(r))
         return out
+
+    def finish_keys(self):
+        """the finish that ends at the key list (mk_sketch_finish_keys) -> (keys device pointer, counts device pointer, n): the
+        engine's own arrays (u64 keys, u32 counts), valid until the next call that begins or finishes a sketch"""
+        k, c, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        _check(lib.mk_sketch_finish_keys(self.h, C.byref(k), C.byref(c), C.byref(n)), self.h)
+        return k.value or 0, c.value or 0, n.value
 
     def batch_begin(self, texts, mode=MK_MODE_SET, one_buffer=False):
         """mk_sketch_batch_begin over a list of byte strings (FASTA texts).  one_buffer: lay the texts into ONE
@@ -1321,6 +1330,10 @@ class Composite:
         index = np.ascontiguousarray(index, dtype=np.uint64)
         self._check(lib.mk_composite_query_component(self.h, c, ids.ctypes.data if ids.size else None,
                                                      counts.ctypes.data if counts.size else None, index.ctypes.data))
+
+    def query_sample_keys(self, k, keys_ptr, counts_ptr, n, comp_code_bits):
+        """sample k of the batch as a device list of n distinct keys (u64) and their counts (u32): mk_composite_query_sample_keys"""
+        self._check(lib.mk_composite_query_sample_keys(self.h, k, C.c_void_p(keys_ptr or None), C.c_void_p(counts_ptr or None), n, comp_code_bits))
 
     def query_finish(self, nsamples):
         """-> per sample a COMPOSITE_ROW array in print order"""

@@ -109,6 +109,11 @@ typedef struct {
   int batch_files;         /* --batch-files */
   int batch_narrow;        /* --batch-narrow: rows of 152 bases (the FASTQ rows) instead of wide rows of 240 */
   int batch_text;          /* --batch-text: the files' TEXT goes to the device (which then does the FASTA walk too) */
+  const char *composite_db; /* --composite <markerdb>: dist -A hands every sample's key list to mk_composite on the device and prints the species
+                            * report; no sketch directory is written */
+  int abv;                 /* --abv: composite's -b (one .abv per sample instead of the report lines) */
+  const char *abv_dir;     /* --abv-dir: composite's -o */
+  int outdir_given, occ_given, batch_given; /* -o, -n / -Q and --batch-mib were on the command line (--composite refuses the first two) */
 } cli_opts;
 extern cli_opts g_opt; /* the one instance (metakssd_main.c, with the defaults) */
 extern double g_t0;    /* process start (monotonic) */
@@ -118,6 +123,10 @@ void load_shuf_params(const char *shuf_path, mk_shuf *sh, mk_params *P);
 void usage(void) __attribute__((noreturn));
 int cmd_set(int argc, char **argv);
 int cmd_composite(int argc, char **argv);
+/* cli_composite.c: one sample's rows, in print order, as the report line or (binvec) as its .abv; vec: room for ref_num + 1 entries */
+typedef struct { int ref_idx; float pct; } composite_vec;
+void composite_write_sample(const mk_composite_row *rows, uint64_t nrows, const char *qname, const char *refname, const char *refdir,
+                            const char *outdir, int binvec, composite_vec *vec);
 int cmd_shuffle(int argc, char **argv);
 int cmd_reverse(int argc, char **argv);
 int cmd_dist_byread(int argc, char **argv);

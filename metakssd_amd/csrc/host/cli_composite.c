@@ -260,8 +260,7 @@ static int composite_search(const char *refdir, int metric, int nargs, char **ar
 }
 /* one sample's rows, in print order, as the report line (command_composite.c:624) or as its .abv (:587-595, :615-636); the two float
  * divisions and the running float sum are the reference's, on the host */
-typedef struct { int ref_idx; float pct; } composite_vec;
-static void composite_write_sample(const mk_composite_row *rows, uint64_t nrows, const char *qname, const char *refname, const char *refdir,
+void composite_write_sample(const mk_composite_row *rows, uint64_t nrows, const char *qname, const char *refname, const char *refdir,
                                    const char *outdir, int binvec, composite_vec *vec) {
   char path[PATHLEN * 3 + 64];
   FILE *vf = NULL;

@@ -70,6 +70,10 @@ typedef struct {
   uint8_t *arena; /* row-buffer pool of the FASTQ stream: an anonymous mapping, pinned piece by piece behind the framers (pin_*) */
   size_t arena_bytes;
   struct pinner *pin;
+  int want_keys; /* dist -A --composite: the finish ends at the engine's key list (mk_sketch_finish_keys), which keys / kcnt / nkeys then name */
+  const uint64_t *keys;
+  const uint32_t *kcnt;
+  uint64_t nkeys;
   int bgzf_ok; /* one engine on one GPU: a BGZF-compressed FASTQ is inflated on the device (sketch_fastq_bgzf): on the -A reader by default,
                 * on the -n / -Q reader with --device-inflate */
 } ctx_t;
@@ -858,7 +862,8 @@ static void sketch_file_finish(ctx_t *c, const job_opts *o, int i, int held, mk_
   if (c->multi) {
     rc = g_multi.finish(c->multi, res, &c->gather_ms, &c->tail_ms);
     if (rc != MK_OK && rc != MK_ERR_CROWDED) die("mk_multi_finish failed (%d): %s", rc, g_multi.last_error(c->multi));
-  } else rc = mk_sketch_finish(eng, res);
+  } else if (c->want_keys) rc = mk_sketch_finish_keys(eng, &c->keys, &c->kcnt, &c->nkeys);
+  else rc = mk_sketch_finish(eng, res);
   *t_finish += now_s() - tf;
   if (held >= 0) {
     pthread_mutex_lock(&pf->mu);
@@ -1078,9 +1083,40 @@ static void *breader_run(void *arg) {
 #ifndef MK_DEFAULT_ENGINES
 #define MK_DEFAULT_ENGINES 2
 #endif
+/* dist -A --composite: the marker database is loaded by a thread of its own while the first file is read; every
+ * sample's key list then goes from the engine to the handle on the device, and a batch is flushed through the report when it holds
+ * batch_limit bytes of ids and at the end */
+typedef struct {
+  pthread_t th;
+  int on, joined, device, rhave;
+  const char *refdir, *abv_dir;
+  costat rs;
+  mk_composite *h;
+  composite_vec *vec;
+  uint64_t *row_end;
+  int batch_first, batch_n; /* the open batch: its first file, its samples so far */
+  uint64_t batch_ids_bytes, batch_limit, batches, hits;
+  double load_ms, query_ms;
+} fused_t;
+static void *fused_load_run(void *arg) { /* as composite_resident() loads it (cli_composite.c) */
+  fused_t *f = arg;
+  const int ref_n = f->rs.infile_num, comp_num = f->rs.comp_num;
+  if (mk_composite_create(f->device, &f->h) != MK_OK) die("mk_composite_create failed: %s", mk_composite_last_error(NULL));
+  if (mk_composite_load_begin(f->h, (uint32_t)ref_n, (uint32_t)comp_num) != MK_OK) die("get_species_abundance(): %s", mk_composite_last_error(f->h));
+  for (int c = 0; c < comp_num; c++) {
+    size_t n1, n2;
+    uint8_t *rco = need_part("get_species_abundance():", f->refdir, "combco", c, 0, &n1);
+    uint8_t *ridx = need_part("get_species_abundance():", f->refdir, "combco.index", c, 8 * ((size_t)ref_n + 1), &n2);
+    if (((const uint64_t *)ridx)[ref_n] * 4 > n1) die("get_species_abundance(): component %d is shorter than its index says", c);
+    if (mk_composite_load_component(f->h, (uint32_t)c, (const uint32_t *)rco, (const uint64_t *)ridx) != MK_OK)
+      die("get_species_abundance(): %s", mk_composite_last_error(f->h));
+    free(rco); free(ridx);
+  }
+  return NULL;
+}
 /* what one run of stage I carries from the plan through one of the four file loops to the --timing line */
 typedef struct {
-  strlist files; mk_shuf sh; mk_params P; mk_sketchdir *sd;
+  strlist files; mk_shuf sh; mk_params P; mk_sketchdir *sd; fused_t fu;
   job_opts jo; ctx_t c; engine_future fut; pf_t pf; extra_engines_t extra;
   int quiet, stage2_after, shard_files, use_batch, n_engines, nthreads, nbatches_done;
   int done_files;     /* the batch loop's progress count */
@@ -1107,10 +1143,46 @@ static void emit_result(stage1 *s, int file, mk_engine *owner, mk_result *res) {
   if (owner) mk_result_release(owner, res);
   if (!s->quiet) printf("%d/%d decomposing %s\r", s->use_batch ? ++s->done_files : file + 1, s->files.n, path);
 }
+/* the open batch through the report: the lines (or .abv files) of its samples, in file order */
+static void fused_flush(stage1 *s) {
+  fused_t *f = &s->fu;
+  if (!f->batch_n) return;
+  const mk_composite_row *rows = NULL;
+  if (mk_composite_query_finish(f->h, &rows, f->row_end) != MK_OK) die("get_species_abundance(): %s", mk_composite_last_error(f->h));
+  for (int k = 0; k < f->batch_n; k++) {
+    const uint64_t lo = k ? f->row_end[k - 1] : 0;
+    composite_write_sample(rows + lo, f->row_end[k] - lo, s->files.v[f->batch_first + k], f->rs.names, f->refdir, f->abv_dir, g_opt.abv, f->vec);
+  }
+  uint64_t bh = 0, br = 0;
+  double lm = 0.0, qm = 0.0;
+  mk_composite_last_counts(f->h, &bh, &br);
+  mk_composite_last_kernel_ms(f->h, &lm, &qm);
+  f->hits += bh; f->query_ms += qm; f->load_ms = lm;
+  f->batches++;
+  f->batch_n = 0; f->batch_ids_bytes = 0;
+}
+/* the file's sketch has ended at the engine's key list (ctx_t::keys): it becomes the next sample of the open batch.  The batch is
+ * begun with room for every file still to come; it is finished as soon as it holds batch_limit bytes of ids (the samples that have
+ * not come by then are empty and print nothing) */
+static void fused_sample(stage1 *s, int file) {
+  fused_t *f = &s->fu;
+  const ctx_t *c = &s->c;
+  if (!f->joined) { pthread_join(f->th, NULL); f->joined = 1; }
+  if (!f->batch_n) {
+    if (mk_composite_query_begin(f->h, (uint32_t)(s->files.n - file)) != MK_OK) die("get_species_abundance(): %s", mk_composite_last_error(f->h));
+    f->batch_first = file;
+  }
+  if (mk_composite_query_sample_keys(f->h, (uint32_t)f->batch_n, c->keys, c->kcnt, c->nkeys, (uint32_t)s->P.comp_code_bits) != MK_OK)
+    die("get_species_abundance(): %s", mk_composite_last_error(f->h));
+  f->batch_n++;
+  f->batch_ids_bytes += c->nkeys * 4;
+  if (f->batch_ids_bytes >= f->batch_limit || file + 1 == s->files.n) fused_flush(s);
+}
 static void sketch_and_emit(stage1 *s, int file) { /* one file alone on the first engine */
   mk_result res;
   sketch_one_file(&s->c, &s->jo, file, &res, &s->t_finish);
-  emit_result(s, file, s->c.eng, &res);
+  if (s->fu.on) fused_sample(s, file);
+  else emit_result(s, file, s->c.eng, &res);
 }
 /* which inputs can travel in batches: plain FASTA files of moderate size, when the device parses the text and one engine works;
  * then (two of them at least) the jobs in input order: runs of eligible files cut into batches, every other file alone */
@@ -1121,7 +1193,7 @@ static void plan_batches(stage1 *s, batch_run *b) {
   uint8_t *elig = s->elig = calloc((size_t)files->n, 1);
   uint32_t *gz_isize = s->gz_isize = calloc((size_t)files->n, sizeof *gz_isize);
   if (!fsize || !elig || !gz_isize) die("out of memory");
-  if (files->n <= 1 || o->no_batch || o->host_fasta || o->engines_per_gpu || s->shard_files || o->ndev > 1) return;
+  if (files->n <= 1 || o->no_batch || o->host_fasta || o->engines_per_gpu || s->shard_files || o->ndev > 1 || o->composite_db) return;
   const uint64_t gun_S = s->gun_S, gun_R = s->gun_R;
   int n_elig = 0;
   if (o->batch_files < 1 || o->batch_files > (int)MK_BATCH_MAX_FILES) die("--batch-files takes 1..%u", MK_BATCH_MAX_FILES);
@@ -1437,6 +1509,7 @@ static void run_engines(stage1 *s) {
     while (have < ready) { /* a new engine: its own buffers for files that stream */
       cx[have] = cx[0];
       cx[have].io = NULL; cx[have].rows = NULL; cx[have].arena = NULL; cx[have].arena_bytes = 0; cx[have].nrows_total = 0;
+      cx[have].pin = NULL; /* (the first engine's pinner stays the first engine's: cli_sink_alloc destroys the one it finds beside a new arena) */
       cx[have].eng = extra->eng[have - 1]; cx[have].engs[0] = extra->eng[have - 1]; cx[have].ndev = 1; cx[have].multi = NULL;
       engine_apply_options(&cx[have], cx[have].eng);
       have++;
@@ -1532,6 +1605,16 @@ int run_stage1(int stage2_after) {
   s->quiet = o->quiet; s->stage2_after = stage2_after; s->nthreads = o->nthreads;
   discover(files, o->args.n, o->args.v);
   if (files->n == 0) die("not valid raw seq format");
+  fused_t *fu = &s->fu;
+  if (o->composite_db) { /* (the other refusals of the fused route: dist_dispatch(); all of them before the device is touched) */
+    for (int i = 0; i < files->n; i++)
+      if (!is_fastq(files->v[i])) die("--composite takes FASTQ inputs: %s is none", files->v[i]);
+    fu->on = 1; fu->refdir = o->composite_db; fu->abv_dir = o->abv_dir ? o->abv_dir : "./"; fu->device = device;
+    fu->batch_limit = o->batch_given ? (uint64_t)o->batch_bytes : 256ull << 20; /* composite's --batch-mib */
+    o->batch_bytes = 0;
+    fu->rhave = costat_load(fu->refdir, &fu->rs);
+    if (fu->rhave == COSTAT_ABSENT) die("cannot find cofiles.stat under %s ", fu->refdir);
+  }
 
   const double t0 = g_t0;
   /* HIP start-up and then the engine's tables on a helper thread; the main thread reads the .shuf file meanwhile and goes
@@ -1541,7 +1624,19 @@ int run_stage1(int stage2_after) {
   const int shard_files = s->shard_files = ndev > 1 && files->n > 1;
   engine_start(&s->fut, ndev ? o->devs[0] : device, o->devs, shard_files ? 0 : ndev, o->allow_copies ? MK_MULTI_ALLOW_DEVICE_COPIES : 0u);
   mk_params *P = &s->P;
+  /* the marker database goes up beside the engine's start-up and the first file's reading; fused_sample() waits for it */
+  if (fu->on && pthread_create(&fu->th, NULL, fused_load_run, fu) != 0) die("cannot start a thread: %s", strerror(errno));
   load_shuf_params(o->shuf_path, &s->sh, P);
+  if (fu->on) { /* cmd_composite()'s checks of the two headers, in its order */
+    if ((uint32_t)P->shuf_id != fu->rs.shuf_id) printf("get_species_abundance(): qry shuf_id %u not match ref shuf_id: %u\n", (uint32_t)P->shuf_id, fu->rs.shuf_id);
+    if (fu->rhave < COSTAT_FULL) die("get_species_abundance(): truncated cofiles.stat");
+    if (fu->rs.comp_num != P->component_num || P->component_num > 16)
+      die("--composite: the marker database has %d components, the sketch %d (equal and at most 16)", fu->rs.comp_num, P->component_num);
+    fu->vec = malloc(8 * ((size_t)fu->rs.infile_num + 1));
+    fu->row_end = malloc(8 * ((size_t)files->n + 1));
+    if (!fu->vec || !fu->row_end) die("out of memory");
+    s->c.want_keys = 1;
+  }
   if (!s->quiet) printf("rand_id=%d\thalf_ctx_len=%d\thashsize=%u\thashlimit=%u\n", P->shuf_id, P->k, P->hashsize, P->hashlimit);
   s->t_shuf = now_s() - t0;
 
@@ -1565,7 +1660,7 @@ int run_stage1(int stage2_after) {
    * engines beside a working one takes 0.04 to 1 s each, two pay, more do not.  --engines 1 turns it off */
   if (o->engines_per_gpu < 0 || o->engines_per_gpu > MAX_ENGINES_PER_GPU) die("--engines takes 1..%d", MAX_ENGINES_PER_GPU);
   plan_batches(s, &B);
-  const int n_engines = s->n_engines = (!s->use_batch && !shard_files && ndev <= 1 && files->n >= 8) ? (o->engines_per_gpu ? o->engines_per_gpu : MK_DEFAULT_ENGINES) : 1;
+  const int n_engines = s->n_engines = (!s->use_batch && !shard_files && ndev <= 1 && files->n >= 8 && !fu->on) ? (o->engines_per_gpu ? o->engines_per_gpu : MK_DEFAULT_ENGINES) : 1;
   if (n_engines > 1) {
     s->extra.P = P; s->extra.device = ndev ? o->devs[0] : device; s->extra.want = n_engines - 1;
     if (pthread_create(&s->extra.th, NULL, extra_engines_run, &s->extra) != 0) die("cannot start a thread: %s", strerror(errno));
@@ -1587,7 +1682,7 @@ int run_stage1(int stage2_after) {
   for (int i = files->n - 1; i >= 0; i--)
     if (!is_fastq(files->v[i])) first_nonfq = i;
   const int koc_dir = o->abundance && first_nonfq == files->n;
-  int rc = mk_sketchdir_open(o->outdir, P, koc_dir, files->n, &s->sd);
+  int rc = fu->on ? MK_OK : mk_sketchdir_open(o->outdir, P, koc_dir, files->n, &s->sd);
   if (rc != MK_OK) die("cannot create sketch directory %s (%d)", o->outdir, rc);
   s->jo = (job_opts){files, P, o->abundance, o->uniq, first_nonfq, o->kmerocrs, o->kmerqlty, s->nthreads, s->quiet, &s->pf, 0};
   if (files->n > 1 && s->nthreads > 1 && !s->use_batch) start_prefetch(s, first_nonfq);
@@ -1597,11 +1692,14 @@ int run_stage1(int stage2_after) {
   else if (n_engines > 1) run_engines(s);
   else run_serial(s);
   if (!s->quiet) printf("\n");
-  rc = mk_sketchdir_close(s->sd);
+  rc = fu->on ? MK_OK : mk_sketchdir_close(s->sd);
   if (rc != MK_OK) die("closing sketch directory failed (%d)", rc);
   s->t_written = now_s() - t0;
   if (!s->quiet) printf("sketched %llu rows from %d file(s) in %.3f s\n", (unsigned long long)c->nrows_total, files->n, s->t_written);
   if (o->timing) print_timing(s);
+  if (o->timing && fu->on)
+    printf("{\"composite_timing\": {\"route\": \"device\", \"samples\": %d, \"batches\": %llu, \"hits\": %llu, \"load_kernel_ms\": %.3f, \"query_kernel_ms\": %.3f}}\n",
+           files->n, (unsigned long long)fu->batches, (unsigned long long)fu->hits, fu->load_ms, fu->query_ms);
   if (stage2_after) {
     if (c->rows) mk_host_free(c->rows);
     free(c->io);

@@ -69,7 +69,7 @@ static void parse_dist_options(int argc, char **argv) {
   for (int i = 0; i < argc; i++) {
     const int more = i + 1 < argc; /* an option's value follows */
     if (!strcmp(argv[i], "-L") && more) o->shuf_path = argv[++i];
-    else if (!strcmp(argv[i], "-o") && more) o->outdir = argv[++i];
+    else if (!strcmp(argv[i], "-o") && more) { o->outdir = argv[++i]; o->outdir_given = 1; }
     else if (!strcmp(argv[i], "-p") && more) { o->nthreads = atoi(argv[++i]); o->threads_given = 1; } /* host front-end threads */
     else if (!strcmp(argv[i], "-A")) o->abundance = 1;
     else if (!strcmp(argv[i], "-u")) o->uniq = 1;
@@ -77,9 +77,15 @@ static void parse_dist_options(int argc, char **argv) {
       int v = atoi(argv[++i]);
       if (v > 7) { fprintf(stderr, "metakssd: -n argument is larger than Max, it has been set to 7, ignorned -n %d \n", v); v = 7; }
       else if (v < 1) { fprintf(stderr, "metakssd: -n argument is smaller than Min, it has been set to 1, ignorned -n %d \n", v); v = 1; }
-      o->kmerocrs = v;
+      o->kmerocrs = v; o->occ_given = 1;
     }
-    else if (!strcmp(argv[i], "-Q") && more) o->kmerqlty = atoi(argv[++i]); /* :182-185 */
+    else if (!strcmp(argv[i], "-Q") && more) { o->kmerqlty = atoi(argv[++i]); o->occ_given = 1; } /* :182-185 */
+    /* dist -L <x.shuf> -A --composite <markerdb> [--abv [--abv-dir <dir>]] [--device D] <fastq>...: the species report of
+     * `composite -r <markerdb> -q <dir>` without the directory -- every sample's key list stays on the device.
+     * --abv is composite's -b, --abv-dir its -o; --batch-mib is composite's (query ids per batch, 256 by default, 0: a sample a batch) */
+    else if (!strcmp(argv[i], "--composite") && more) { o->composite_db = argv[++i]; o->quiet = 1; }
+    else if (!strcmp(argv[i], "--abv")) o->abv = 1;
+    else if (!strcmp(argv[i], "--abv-dir") && more) o->abv_dir = argv[++i];
     else if (!strcmp(argv[i], "--device") && more) o->device = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--devices") && more) o->ndev = parse_devices(argv[++i], o->devs, 64);
     else if (!strcmp(argv[i], "--engines") && more) o->engines_per_gpu = atoi(argv[++i]);
@@ -87,7 +93,7 @@ static void parse_dist_options(int argc, char **argv) {
     else if (!strcmp(argv[i], "--no-batch")) o->no_batch = 1;
     else if (!strcmp(argv[i], "--batch-narrow")) o->batch_narrow = 1;
     else if (!strcmp(argv[i], "--batch-text")) o->batch_text = 1;
-    else if (!strcmp(argv[i], "--batch-mib") && more) o->batch_bytes = (size_t)atoi(argv[++i]) << 20;
+    else if (!strcmp(argv[i], "--batch-mib") && more) { o->batch_bytes = (size_t)atoi(argv[++i]) << 20; o->batch_given = 1; }
     else if (!strcmp(argv[i], "--batch-files") && more) o->batch_files = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--host-fasta")) o->host_fasta = 1;
     else if (!strcmp(argv[i], "--quiet")) o->quiet = 1;
@@ -132,6 +138,18 @@ static int dist_dispatch(void) {
   cli_opts *o = &g_opt;
   strlist *args = &o->args;
   int stage2_after = 0;
+  if (o->composite_db) { /* the fused route: what it cannot do is said before the device is touched */
+    if (!o->abundance) die("--composite needs -A: the report reads the k-mer counts");
+    if (o->occ_given) die("--composite does not take -n or -Q: the report reads every k-mer of the reads");
+    if (o->ndev) die("--composite works on one GPU: --device D, not --devices");
+    if (o->engines_per_gpu > 1) die("--composite works with one engine: not --engines %d", o->engines_per_gpu);
+    if (o->outdir_given) die("--composite keeps the sketch on the device; for a directory run dist -o and composite -q");
+    if (!dir_has(o->composite_db, "cofiles.stat")) die("cannot find cofiles.stat under %s ", o->composite_db);
+    if (!o->shuf_path) die("-L <file.shuf> is required (numeric levels generate a time-seeded table in the reference; use `metakssd shuffle`)");
+    if (args->n == 0) die("please specify the input/query files");
+    o->quiet = 1; o->refpath = NULL;
+    return run_stage1(0);
+  }
   if (o->refpath) {
     if (o->dopt.metric < 0 || o->dopt.metric > 1 || o->dopt.outfields < 0 || o->dopt.outfields > 2) die("-M takes 0/1 and -O 0/1/2");
     struct stat rst;

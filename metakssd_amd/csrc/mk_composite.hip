@@ -16,6 +16,11 @@
  *                             first occurrence of an id in a sample (command_composite.c:538-546, :551-554)
  *     mkc_winner_kernel       a position that is not the minimum of its key loses its row; the others add their row's length to
  *                             the sample's hit count
+ *   a sample that arrives as a device key list (mk_composite_query_sample_keys)
+ *     mkc_part_count_kernel   per-block LDS histogram of key % comp_num -> the sample's size in every component
+ *     mkc_part_scatter_kernel (id, count) of every key appended to its component's query arrays; order inside a slice is free
+ *     mkc_lookup_kernel<true>, mkc_winner_kernel<true>  at the finish of such a batch: the keys of a sample are distinct, so no id
+ *                             repeats in a sample, the (sample, id) table is not needed and every position with a row counts
  *   finish, per sub-range of whole samples (hits <= the hit buffer, samples * ref_num <= 2^32 - 1)
  *     mkc_count/scan/emit<HitF>   per component: one hit (segment = local sample * ref_num + sketch, count) per row entry, all
  *                             components into one buffer (the reference accumulates over components before it sorts, :496-574)
@@ -52,6 +57,8 @@ namespace { /* mk_mco.hip and mk_abv.hip hold the sort's kernels too: this file'
 #define MKC_MIN_KM 6u                  /* MIN_KM_S */
 #define MKC_BUCKET_BITS 20u            /* at most 2^20 buckets (4 MiB) per component */
 #define MKC_DEFAULT_MAX_HITS (1ull << 26) /* 64 M hits: four 256 MiB arrays */
+#define MKC_PART_MAX 16u               /* components a device key list is split into (mk_composite_query_sample_keys) */
+enum { MKC_BATCH_NONE = 0, MKC_BATCH_HOST, MKC_BATCH_DEVICE };
 
 struct mkc_comp {
   bool loaded = false;
@@ -76,6 +83,9 @@ struct mk_composite {
   hipStream_t stream = nullptr;
   uint32_t ref_num = 0, comp_num = 0, nsamples = 0;
   bool load_begun = false, querying = false;
+  int batch_kind = MKC_BATCH_NONE; /* who feeds the current batch: mk_composite_query_component or mk_composite_query_sample_keys */
+  uint32_t next_k = 0;             /* device-fed batch: the sample that comes next */
+  unsigned long long *d_part = nullptr, *h_part = nullptr; /* [2 * MKC_PART_MAX] a key list's component totals and scatter cursors; [MKC_PART_MAX] pinned */
   uint64_t max_hits = MKC_DEFAULT_MAX_HITS;
   std::vector<mkc_comp> comp;
   /* sort scratch, shared by load and finish */
@@ -249,7 +259,57 @@ __device__ __forceinline__ uint64_t mkc_mix(uint64_t x) {
   return x;
 }
 
-/* query position -> its row; positions with a row enter the (sample, id) table, which keeps the smallest position */
+/* ---- a sample as a device key list -> the per-component query arrays ----
+ * Two passes over the list.  The first counts: a histogram over the components per block in LDS, one global add per block and
+ * component.  The host then sizes the query arrays from the totals.  The second counts again, reserves the block's stretch of
+ * every component with one global add each, and hands out the places inside the stretch by LDS adds: any order will do, the ids of a
+ * sample's slice are distinct and nothing downstream reads their order (the hits are sorted by count and segment). */
+struct mkc_part_dst {
+  uint32_t *qids[MKC_PART_MAX];
+  uint16_t *qcnt[MKC_PART_MAX];
+  unsigned long long base[MKC_PART_MAX], cap[MKC_PART_MAX]; /* where the sample's slice begins; entries the arrays hold */
+};
+
+__global__ void __launch_bounds__(MKC_BLOCK) mkc_part_count_kernel(const unsigned long long *keys, uint64_t n, uint32_t comp_num, unsigned long long *totals) {
+  __shared__ uint32_t hist[MKC_PART_MAX];
+  if (threadIdx.x < MKC_PART_MAX) hist[threadIdx.x] = 0u;
+  __syncthreads();
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    atomicAdd(&hist[(uint32_t)(keys[i] % comp_num)], 1u);
+  __syncthreads();
+  if (threadIdx.x < comp_num && hist[threadIdx.x]) atomicAdd(&totals[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(MKC_BLOCK) mkc_part_scatter_kernel(const unsigned long long *keys, const uint32_t *counts, uint64_t n, uint32_t comp_num,
+                                                                    uint32_t comp_code_bits, unsigned long long *cursor, mkc_part_dst dst) {
+  __shared__ uint32_t hist[MKC_PART_MAX];
+  __shared__ unsigned long long start[MKC_PART_MAX];
+  if (threadIdx.x < MKC_PART_MAX) hist[threadIdx.x] = 0u;
+  __syncthreads();
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    atomicAdd(&hist[(uint32_t)(keys[i] % comp_num)], 1u);
+  __syncthreads();
+  if (threadIdx.x < comp_num) {
+    const uint32_t c = threadIdx.x;
+    start[c] = dst.base[c] + (hist[c] ? atomicAdd(&cursor[c], (unsigned long long)hist[c]) : 0ull);
+    hist[c] = 0u;
+  }
+  __syncthreads();
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = keys[i];
+    const uint32_t c = (uint32_t)(key % comp_num);
+    const unsigned long long p = start[c] + atomicAdd(&hist[c], 1u);
+    if (p < dst.cap[c]) { /* (the first pass counted them: always) */
+      const uint32_t v = counts[i];
+      dst.qids[c][p] = (uint32_t)(key >> comp_code_bits);
+      dst.qcnt[c][p] = (uint16_t)(v > 65535u ? 65535u : v);
+    }
+  }
+}
+
+/* query position -> its row; positions with a row enter the (sample, id) table, which keeps the smallest position.  DISTINCT: the
+ * batch came as key lists, no id repeats in a sample: no table (tkey, tpos are not read) */
+template <bool DISTINCT>
 __global__ void __launch_bounds__(MKC_BLOCK) mkc_lookup_kernel(const uint32_t *qids, uint64_t nq, const unsigned long long *qindex, uint32_t nsamples,
                                                               const uint32_t *row_ids, const uint32_t *bucket, uint32_t shift, uint32_t nbuckets,
                                                               unsigned long long *tkey, uint32_t *tpos, uint64_t tmask, uint32_t *rowidx) {
@@ -263,7 +323,7 @@ __global__ void __launch_bounds__(MKC_BLOCK) mkc_lookup_kernel(const uint32_t *q
       if (r < hi && row_ids[r] == id) row = (uint32_t)r;
     }
     rowidx[i] = row;
-    if (row == MKC_NONE) continue;
+    if (DISTINCT || row == MKC_NONE) continue;
     const uint64_t s = mkc_upper(qindex, 0, (uint64_t)nsamples + 1, (unsigned long long)i) - 1;
     const unsigned long long k = ((unsigned long long)s << 32) | id;
     for (uint64_t slot = mkc_mix(k) & tmask;; slot = (slot + 1) & tmask) { /* at most half of the slots are ever taken */
@@ -273,6 +333,8 @@ __global__ void __launch_bounds__(MKC_BLOCK) mkc_lookup_kernel(const uint32_t *q
   }
 }
 
+/* DISTINCT: every position with a row is the only one of its (sample, id) and adds its row's length */
+template <bool DISTINCT>
 __global__ void __launch_bounds__(MKC_BLOCK) mkc_winner_kernel(const uint32_t *qids, uint64_t nq, const unsigned long long *qindex, uint32_t nsamples,
                                                               const uint32_t *row_start, const unsigned long long *tkey, const uint32_t *tpos,
                                                               uint64_t tmask, uint32_t *rowidx, unsigned long long *sample_hits) {
@@ -280,10 +342,12 @@ __global__ void __launch_bounds__(MKC_BLOCK) mkc_winner_kernel(const uint32_t *q
     const uint32_t row = rowidx[i];
     if (row == MKC_NONE) continue;
     const uint64_t s = mkc_upper(qindex, 0, (uint64_t)nsamples + 1, (unsigned long long)i) - 1;
-    const unsigned long long k = ((unsigned long long)s << 32) | qids[i];
-    uint64_t slot = mkc_mix(k) & tmask;
-    while (tkey[slot] != k) slot = (slot + 1) & tmask; /* it is there: mkc_lookup_kernel put it in */
-    if (tpos[slot] != (uint32_t)i) { rowidx[i] = MKC_NONE; continue; } /* a repeat of an id in its sample: the first occurrence counts */
+    if (!DISTINCT) {
+      const unsigned long long k = ((unsigned long long)s << 32) | qids[i];
+      uint64_t slot = mkc_mix(k) & tmask;
+      while (tkey[slot] != k) slot = (slot + 1) & tmask; /* it is there: mkc_lookup_kernel put it in */
+      if (tpos[slot] != (uint32_t)i) { rowidx[i] = MKC_NONE; continue; } /* a repeat of an id in its sample: the first occurrence counts */
+    }
     atomicAdd(&sample_hits[s], (unsigned long long)(row_start[row + 1] - row_start[row]));
   }
 }
@@ -389,6 +453,8 @@ extern "C" int mk_composite_create(int device, mk_composite **out) {
   if (r == hipSuccess) r = mk_dev_alloc(&h->d_tmp, (size_t)256 * MK_RS_MAXB * 4 + 256 * 8 + 64);
   if (r == hipSuccess) r = mk_pin_alloc((void **)&h->h_sort_flag, 4 * sizeof(uint32_t), hipHostMallocDefault);
   if (r == hipSuccess) r = mk_pin_alloc((void **)&h->h_word, 16, hipHostMallocDefault);
+  if (r == hipSuccess) r = mk_pin_alloc((void **)&h->h_part, MKC_PART_MAX * sizeof(unsigned long long), hipHostMallocDefault);
+  if (r == hipSuccess) r = mk_dev_alloc((void **)&h->d_part, 2 * MKC_PART_MAX * sizeof(unsigned long long));
   if (r == hipSuccess) r = hipEventCreate(&h->ev[0]);
   if (r == hipSuccess) r = hipEventCreate(&h->ev[1]);
   if (r != hipSuccess) {
@@ -410,6 +476,8 @@ extern "C" int mk_composite_destroy(mk_composite *h) {
   (void)hipFree(h->d_tpos); (void)hipFree(h->d_sample_hits); (void)hipFree(h->d_starts); (void)hipFree(h->d_big); (void)hipFree(h->d_rows);
   if (h->h_sort_flag) (void)hipHostFree(h->h_sort_flag);
   if (h->h_word) (void)hipHostFree(h->h_word);
+  if (h->h_part) (void)hipHostFree(h->h_part);
+  (void)hipFree(h->d_part);
   if (h->h_sample_hits) (void)hipHostFree(h->h_sample_hits);
   if (h->h_rows) (void)hipHostFree(h->h_rows);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -590,6 +658,7 @@ extern "C" int mk_composite_query_begin(mk_composite *h, uint32_t nsamples) {
   if (rc) return rc;
   MKC_HIP(h, hipMemsetAsync(h->d_sample_hits, 0, ((size_t)nsamples + 1) * 8, h->stream));
   for (auto &c : h->comp) { c.have = false; c.nq = 0; }
+  h->batch_kind = MKC_BATCH_NONE; h->next_k = 0;
   h->nsamples = nsamples;
   h->query_ms = 0.0;
   h->hits = 0; h->ranges = 0;
@@ -601,6 +670,7 @@ extern "C" int mk_composite_query_component(mk_composite *h, uint32_t ci, const 
   if (!h || !index) return MK_ERR_ARG;
   if (!h->load_begun || !h->querying) return mkc_fail(h, MK_ERR_STATE, "mk_composite_query_component before mk_composite_query_begin");
   if (ci >= h->comp_num) return mkc_fail(h, MK_ERR_ARG, "component %u of %u", ci, h->comp_num);
+  if (h->batch_kind == MKC_BATCH_DEVICE) return mkc_fail(h, MK_ERR_STATE, "mk_composite_query_component in a batch fed by mk_composite_query_sample_keys");
   mkc_comp &c = h->comp[ci];
   if (c.have) return mkc_fail(h, MK_ERR_STATE, "component %u given twice in one batch", ci);
   const uint32_t S = h->nsamples;
@@ -612,6 +682,7 @@ extern "C" int mk_composite_query_component(mk_composite *h, uint32_t ci, const 
     if (index[j] > index[j + 1]) return mkc_fail(h, MK_ERR_ARG, "the batch's positions are not ascending at sample %u", j);
   MKC_HIP(h, hipSetDevice(h->device));
   try { c.qindex.assign(index, index + (size_t)S + 1); } catch (...) { return mkc_fail(h, MK_ERR_NOMEM, "out of memory"); }
+  h->batch_kind = MKC_BATCH_HOST;
   c.have = true;
   c.nq = nq;
   if (nq == 0 || c.nrows == 0) { c.nq = 0; return MK_OK; } /* nothing of this component can hit */
@@ -630,15 +701,107 @@ extern "C" int mk_composite_query_component(mk_composite *h, uint32_t ci, const 
   if ((rc = mkc_time_begin(h))) return rc;
   MKC_HIP(h, hipMemsetAsync(h->d_tkey, 0xFF, slots * 8, h->stream));
   MKC_HIP(h, hipMemsetAsync(h->d_tpos, 0xFF, slots * 4, h->stream));
-  hipLaunchKernelGGL(mkc_lookup_kernel, dim3(mkc_blocks(h, nq)), dim3(MKC_BLOCK), 0, h->stream, (const uint32_t *)c.d_qids, nq,
+  hipLaunchKernelGGL(mkc_lookup_kernel<false>, dim3(mkc_blocks(h, nq)), dim3(MKC_BLOCK), 0, h->stream, (const uint32_t *)c.d_qids, nq,
                      (const unsigned long long *)c.d_qindex, S, (const uint32_t *)c.d_row_ids, (const uint32_t *)c.d_bucket, c.shift, c.nbuckets,
                      h->d_tkey, h->d_tpos, slots - 1, c.d_rowidx);
-  hipLaunchKernelGGL(mkc_winner_kernel, dim3(mkc_blocks(h, nq)), dim3(MKC_BLOCK), 0, h->stream, (const uint32_t *)c.d_qids, nq,
+  hipLaunchKernelGGL(mkc_winner_kernel<false>, dim3(mkc_blocks(h, nq)), dim3(MKC_BLOCK), 0, h->stream, (const uint32_t *)c.d_qids, nq,
                      (const unsigned long long *)c.d_qindex, S, (const uint32_t *)c.d_row_start, (const unsigned long long *)h->d_tkey,
                      (const uint32_t *)h->d_tpos, slots - 1, c.d_rowidx, h->d_sample_hits);
   MKC_HIP(h, hipGetLastError());
   if ((rc = mkc_time_end(h, &h->query_ms))) return rc; /* (waits: the caller's arrays are free again) */
   return MK_OK;
+}
+
+/* a query array that grows and keeps its first `keep` entries (the samples a device-fed batch has taken already) */
+template <class T>
+static int mkc_grow_keep(mk_composite *h, T **p, uint64_t *cap, uint64_t need, uint64_t keep) {
+  if (need <= *cap && *p) return MK_OK;
+  T *np = nullptr;
+  const uint64_t c = need + need / 2 + 1024;
+  hipError_t r = mk_dev_alloc((void **)&np, c * sizeof(T));
+  if (r != hipSuccess) return mkc_fail(h, MK_ERR_NOMEM, "device allocation of %llu bytes: %s", (unsigned long long)(c * sizeof(T)), hipGetErrorString(r));
+  if (keep && *p) {
+    r = hipMemcpyAsync(np, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, h->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(h->stream); /* the old array goes now */
+    if (r != hipSuccess) { (void)hipFree(np); return mkc_fail(h, MK_ERR_HIP, "copying a query array: %s", hipGetErrorString(r)); }
+  }
+  (void)hipFree(*p);
+  *p = np; *cap = c;
+  return MK_OK;
+}
+
+extern "C" int mk_composite_query_sample_keys(mk_composite *h, uint32_t k, const uint64_t *keys_dev, const uint32_t *counts_dev, uint64_t n,
+                                              uint32_t comp_code_bits) {
+  if (!h) return MK_ERR_ARG;
+  if (!h->load_begun || !h->querying) return mkc_fail(h, MK_ERR_STATE, "mk_composite_query_sample_keys before mk_composite_query_begin");
+  if (h->batch_kind == MKC_BATCH_HOST) return mkc_fail(h, MK_ERR_STATE, "mk_composite_query_sample_keys in a batch fed by mk_composite_query_component");
+  const uint32_t C = h->comp_num;
+  if (C > MKC_PART_MAX) return mkc_fail(h, MK_ERR_ARG, "mk_composite_query_sample_keys: %u components (at most %u are supported)", C, MKC_PART_MAX);
+  if (comp_code_bits >= 32u || (1u << comp_code_bits) != C)
+    return mkc_fail(h, MK_ERR_ARG, "mk_composite_query_sample_keys: comp_code_bits %u does not go with the database's %u components", comp_code_bits, C);
+  if (k != h->next_k || k >= h->nsamples)
+    return mkc_fail(h, MK_ERR_ARG, "mk_composite_query_sample_keys: sample %u, expected %u of %u (samples come in ascending order)", k, h->next_k, h->nsamples);
+  if (n && (!keys_dev || !counts_dev)) return MK_ERR_ARG;
+  if (n >= 0xFFFFFFFFull) return mkc_fail(h, MK_ERR_ARG, "mk_composite_query_sample_keys: a sample of %llu keys (fewer than 2^32 - 1 are supported)", (unsigned long long)n);
+  MKC_HIP(h, hipSetDevice(h->device));
+  if (h->batch_kind == MKC_BATCH_NONE) /* positions of the samples taken so far, per component: [0] */
+    try { for (auto &c : h->comp) c.qindex.assign(1, 0); } catch (...) { return mkc_fail(h, MK_ERR_NOMEM, "out of memory"); }
+  h->batch_kind = MKC_BATCH_DEVICE;
+  int rc;
+  if (n) {
+    if ((rc = mkc_time_begin(h))) return rc;
+    MKC_HIP(h, hipMemsetAsync(h->d_part, 0, 2 * MKC_PART_MAX * sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(mkc_part_count_kernel, dim3(mkc_blocks(h, n)), dim3(MKC_BLOCK), 0, h->stream, (const unsigned long long *)keys_dev, n, C, h->d_part);
+    MKC_HIP(h, hipGetLastError());
+    MKC_HIP(h, hipMemcpyAsync(h->h_part, h->d_part, MKC_PART_MAX * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    MKC_HIP(h, hipStreamSynchronize(h->stream));
+    uint64_t sum = 0;
+    for (uint32_t ci = 0; ci < C; ci++) sum += h->h_part[ci];
+    if (sum != n) return mkc_fail(h, MK_ERR_STATE, "mk_composite_query_sample_keys: %llu keys counted, %llu given", (unsigned long long)sum, (unsigned long long)n);
+    mkc_part_dst dst{};
+    for (uint32_t ci = 0; ci < C; ci++) {
+      mkc_comp &c = h->comp[ci];
+      const uint64_t need = c.nq + h->h_part[ci];
+      if (need >= 0xFFFFFFFFull) return mkc_fail(h, MK_ERR_ARG, "mk_composite_query_sample_keys: a batch of %llu ids in one component (fewer than 2^32 - 1 are supported)", (unsigned long long)need);
+      if (need) {
+        if ((rc = mkc_grow_keep(h, &c.d_qids, &c.q_cap, need, c.nq))) return rc;
+        if ((rc = mkc_grow_keep(h, &c.d_qcnt, &c.qcnt_cap, need, c.nq))) return rc;
+      }
+      dst.qids[ci] = c.d_qids; dst.qcnt[ci] = c.d_qcnt; dst.base[ci] = c.nq; dst.cap[ci] = need;
+    }
+    hipLaunchKernelGGL(mkc_part_scatter_kernel, dim3(mkc_blocks(h, n)), dim3(MKC_BLOCK), 0, h->stream, (const unsigned long long *)keys_dev, counts_dev, n, C,
+                       comp_code_bits, h->d_part + MKC_PART_MAX, dst);
+    MKC_HIP(h, hipGetLastError());
+    if ((rc = mkc_time_end(h, &h->query_ms))) return rc; /* (waits for the handle's stream: the caller's list has been read) */
+    for (uint32_t ci = 0; ci < C; ci++) h->comp[ci].nq += h->h_part[ci];
+  }
+  try { for (auto &c : h->comp) c.qindex.push_back(c.nq); } catch (...) { return mkc_fail(h, MK_ERR_NOMEM, "out of memory"); }
+  h->next_k = k + 1;
+  return MK_OK;
+}
+
+/* a device-fed batch is complete: per component the positions of its samples go up and every position finds its row; no table */
+static int mkc_lookup_distinct(mk_composite *h) {
+  const uint32_t S = h->nsamples;
+  int rc;
+  if ((rc = mkc_time_begin(h))) return rc;
+  for (auto &c : h->comp) {
+    c.have = c.nq != 0;
+    if (!c.have) continue;
+    try { c.qindex.resize((size_t)S + 1, c.nq); } catch (...) { return mkc_fail(h, MK_ERR_NOMEM, "out of memory"); } /* samples that never came are empty */
+    if ((rc = mkc_grow(h, &c.d_rowidx, &c.rowidx_cap, c.nq))) return rc;
+    if ((rc = mkc_grow(h, &c.d_qindex, &c.qindex_cap, (uint64_t)S + 1))) return rc;
+    MKC_HIP(h, hipMemcpyAsync(c.d_qindex, c.qindex.data(), ((size_t)S + 1) * 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(mkc_lookup_kernel<true>, dim3(mkc_blocks(h, c.nq)), dim3(MKC_BLOCK), 0, h->stream, (const uint32_t *)c.d_qids, c.nq,
+                       (const unsigned long long *)c.d_qindex, S, (const uint32_t *)c.d_row_ids, (const uint32_t *)c.d_bucket, c.shift, c.nbuckets,
+                       (unsigned long long *)nullptr, (uint32_t *)nullptr, (uint64_t)0, c.d_rowidx);
+    hipLaunchKernelGGL(mkc_winner_kernel<true>, dim3(mkc_blocks(h, c.nq)), dim3(MKC_BLOCK), 0, h->stream, (const uint32_t *)c.d_qids, c.nq,
+                       (const unsigned long long *)c.d_qindex, S, (const uint32_t *)c.d_row_start, (const unsigned long long *)nullptr,
+                       (const uint32_t *)nullptr, (uint64_t)0, c.d_rowidx, h->d_sample_hits);
+    MKC_HIP(h, hipGetLastError());
+  }
+  /* (the copies above read the host vectors: waited for before anyone may change them) */
+  return mkc_time_end(h, &h->query_ms);
 }
 
 /* samples [s0, s1) with `tot` hits between them: their rows, in (sample, reference) order, appended to h->rows / h->row_sample */
@@ -716,6 +879,10 @@ extern "C" int mk_composite_query_finish(mk_composite *h, const mk_composite_row
   h->row_sample.clear();
   *rows = nullptr;
   if (S == 0) return MK_OK;
+  if (h->batch_kind == MKC_BATCH_DEVICE) {
+    const int lrc = mkc_lookup_distinct(h);
+    if (lrc) return lrc;
+  }
   if (S > h->h_sample_cap || !h->h_sample_hits) {
     if (h->h_sample_hits) (void)hipHostFree(h->h_sample_hits);
     h->h_sample_hits = nullptr; h->h_sample_cap = 0;

@@ -2128,6 +2128,44 @@ static int mk_finish_impl(mk_engine *e, mk_result *out, bool staged) {
   return MK_OK;
 }
 
+/* The finish that ends at the key list: the compaction and nothing behind it -- no priority layout, no dump, no copy of
+ * ids to the host.  With MK_MODE_KOC every entry of the list is an entry of the sketch (the dump's count window is [1, 2^32) there and
+ * the compaction keeps key 0), so the list IS the sketch as a multiset of (key % component_num, key >> comp_code_bits, count); only
+ * the reference's slot order is missing, and who asks for the list does not read it. */
+extern "C" int mk_sketch_finish_keys(mk_engine *e, const uint64_t **keys_dev, const uint32_t **counts_dev, uint64_t *n) {
+  if (!e || !keys_dev || !counts_dev || !n) return MK_ERR_ARG;
+  *keys_dev = nullptr; *counts_dev = nullptr; *n = 0;
+  if (!e->begun) return mk_fail(e, MK_ERR_STATE, "finish before mk_sketch_begin");
+  if (e->res_pending) return mk_fail(e, MK_ERR_STATE, "mk_sketch_finish_keys while the result of mk_sketch_finish_begin has not been taken (mk_sketch_finish_end)");
+  if (e->mode != MK_MODE_KOC) /* (the -n threshold and the uniq rule live in the dump; the sketch stays open) */
+    return mk_fail(e, MK_ERR_ARG, "mk_sketch_finish_keys: MK_MODE_KOC sketches only");
+  MK_HIP(e, hipSetDevice(e->device));
+  mk_evpair ev{};
+  if (e->profiling) { ev = mk_ev_get(e); MK_HIP(e, hipEventRecord(ev.a, e->stream)); }
+  int rc;
+  if (e->count_queued) { /* mk_partial_count_begin has launched the compaction */
+    e->count_queued = false;
+    hipError_t hr = hipStreamSynchronize(e->stream);
+    if (hr != hipSuccess) { if (e->profiling) e->ev_pool.push_back(ev); return mk_fail(e, MK_ERR_HIP, "hipStreamSynchronize: %s", hipGetErrorString(hr)); }
+    rc = mk_check_counters(e);
+    if (rc == MK_OK) rc = mk_dist_fit(e);
+    if (rc == MK_OK) e->compacted = true;
+  } else {
+    rc = mk_compact(e);
+  }
+  if (rc) {
+    if (e->profiling) e->ev_pool.push_back(ev);
+    if (rc == MK_ERR_CROWDED || rc == MK_ERR_FORMAT) e->begun = false; /* the sketch is spent, as after mk_sketch_finish */
+    return rc;
+  }
+  if (e->profiling) { MK_HIP(e, hipEventRecord(ev.b, e->stream)); e->ev_finish.push_back(ev); }
+  *keys_dev = (const uint64_t *)e->dist.key;
+  *counts_dev = e->dist.cnt;
+  *n = e->D;
+  e->begun = false;
+  return MK_OK;
+}
+
 extern "C" int mk_result_release(mk_engine *e, mk_result *r) {
   if (!e || !r) return MK_ERR_ARG;
   r->components = nullptr;
