@@ -265,6 +265,17 @@ int mk_sketch_push_wait(mk_engine *e, uint64_t ticket);
  * ends inside a header line is the reference's "can not find seqences head start from '>'" abort: mk_sketch_finish returns
  * MK_ERR_FORMAT.  May be mixed with mk_sketch_push_reads* in one sketch; ordinals follow the order of the calls. */
 int mk_sketch_push_stream(mk_engine *e, const uint8_t *text, uint64_t n, int final);
+/* FASTQ text as it is in the file, lines of any length (long reads): mt_shortreads2koc() (iseq2comem.c:657-727) with its FQ_LEN (:656)
+ * unbounded.  A record is four lines (:673: four fgets(); a record whose fourth gives nothing is dropped, so a file that ends inside
+ * a record loses that record, and a last quality line counts with or without its '\n'); the second line is walked up to its '\n',
+ * a byte that is no base -- '\r' included -- resets the k-mer window (:682-690); headers, '+' lines and quality lines are never
+ * looked at.  The device keeps the sequence lines of complete records in the base stream of mk_sketch_push_stream, one separator
+ * behind each, and scans the same overlapping rows: no row framing, no length limit below 2^31 bytes a record (MK_ERR_ARG beyond).
+ * For reads under 4 095 characters the sketch is the one mk_sketch_push_fastq and the reference give: ids, counts (saturating at
+ * 65 535), slot order, MK_ERR_CROWDED beyond hashlimit.  Pieces, `final` and the rules for pinned and pageable text are those of
+ * mk_sketch_push_stream; text may be cut anywhere (the record left open by a piece waits in front of the next).  MK_MODE_KOC
+ * sketches only (MK_ERR_STATE otherwise); not to be mixed with mk_sketch_push_stream in one sketch (MK_ERR_STATE). */
+int mk_sketch_push_fastq_long(mk_engine *e, const uint8_t *text, uint64_t n, int final);
 int mk_sketch_finish(mk_engine *e, mk_result *out);
 /* mk_sketch_finish in two halves, for callers that sketch one input after another: _begin runs compaction, layout and dump (into
  * staging arrays in HBM), waits once for the counters and queues the copy of the result to the host on a stream of its own;

@@ -178,6 +178,7 @@ def _load():
         "mk_sketch_push_reads_async": [vp, vp, u32, u64, u64, C.POINTER(u64)],
         "mk_sketch_push_wait": [vp, u64],
         "mk_sketch_push_stream": [vp, vp, u64, C.c_int],
+        "mk_sketch_push_fastq_long": [vp, vp, u64, C.c_int],
         "mk_partial_count_begin": [vp],
         "mk_partial_export_async": [vp, vp, vp, vp, u64, C.POINTER(u64)],
         "mk_pack_rows_host": [vp, u32, u64, vp],
@@ -657,6 +658,23 @@ class Engine:
             last = at + n >= len(b)
             part = np.ascontiguousarray(b[at:at + n])
             _check(lib.mk_sketch_push_stream(self.h, part.ctypes.data if n else None, n, 1 if (last and final) else 0), self.h)
+            at += n
+            if last:
+                break
+
+    def push_fastq_long(self, text, final=True, piece=None):
+        """FASTQ text as it is in the file, lines of any length -> mk_sketch_push_fastq_long; piece: push in pieces of that many bytes
+        (the last one final)"""
+        b = np.frombuffer(bytes(text), dtype=np.uint8)
+        if not piece:
+            _check(lib.mk_sketch_push_fastq_long(self.h, b.ctypes.data if len(b) else None, len(b), 1 if final else 0), self.h)
+            return
+        at = 0
+        while True:
+            n = min(piece, len(b) - at)
+            last = at + n >= len(b)
+            part = np.ascontiguousarray(b[at:at + n])
+            _check(lib.mk_sketch_push_fastq_long(self.h, part.ctypes.data if n else None, n, 1 if (last and final) else 0), self.h)
             at += n
             if last:
                 break

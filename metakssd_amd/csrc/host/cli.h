@@ -100,6 +100,10 @@ typedef struct {
                             * DESIGN.md 4.14) and on the -n / -Q reader (mk_sketch_push_gzip_q).  Opt-in: without the switch such a file keeps zcat */
   int gz_gunzip;           /* --device-gunzip on a directory of genomes: the gz batches are inflated by many wavefronts per file
                             * (mk_sketch_batch_begin_gunzip); decides the genome route when --device-inflate is given too */
+  int long_reads;          /* --long-reads: dist -A on FASTQ lines of any length -- the file's text goes to the device as it is and the sequence
+                            * lines of complete records are scanned from the base stream (mk_sketch_push_fastq_long).  Opt-in:
+                            * without the switch a line of 4 095+ characters is refused as before */
+  int device_inflate_given; /* --device-inflate was on the command line (what --long-reads refuses) */
   mk_gunzip_opts gunzip_opts;   /* --gunzip-span-bytes, --gunzip-ratio, --gunzip-batch-spans (test hooks; 0 = the library's defaults) */
   uint64_t inflate_chunk_bytes; /* --inflate-chunk-kib: text bytes per chunk of the device route (test hook; 0 = the library's default) */
   int component_sz;        /* --component-sz: the reference's compile-time COMPONENT_SZ (global_basic.h:35-37) */

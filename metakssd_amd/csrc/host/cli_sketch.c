@@ -74,6 +74,7 @@ typedef struct {
   const uint64_t *keys;
   const uint32_t *kcnt;
   uint64_t nkeys;
+  uint8_t *long_buf[2]; /* --long-reads: two pinned text buffers, filled in turn (sketch_fastq_long) */
   int bgzf_ok; /* one engine on one GPU: a BGZF-compressed FASTQ is inflated on the device (sketch_fastq_bgzf): on the -A reader by default,
                 * on the -n / -Q reader with --device-inflate */
 } ctx_t;
@@ -565,7 +566,76 @@ static int sketch_fastq_gunzip(ctx_t *c, const char *path) {
   }
   return 1;
 }
+/* --long-reads: the file's text as it is, plain or through `zcat -fc`, in pieces of LONG_CHUNK bytes from two pinned
+ * buffers in turn.  A push of pinned text returns once its copy and kernels are queued and is waited for at the start of the next
+ * one, so buffer k ^ 1 is filled beside the copy and the kernels of buffer k -- two pieces in flight.  No framing on the host and
+ * no limit on a line's length: the device keeps the sequence lines of complete records (mk_sketch_push_fastq_long). */
+#define LONG_CHUNK ((size_t)32 << 20)
+#define LONG_READERS 8
+/* a plain file's next piece comes out of the page cache by several threads: one thread copies 8 GB/s, which alone bounded the route
+ * at 0.52 s for 4 GB of text */
+typedef struct { int fd; uint8_t *dst; off_t off; size_t n, got; } long_part;
+static void *long_part_run(void *arg) {
+  long_part *p = arg;
+  while (p->got < p->n) {
+    const ssize_t r = pread(p->fd, p->dst + p->got, p->n - p->got, p->off + (off_t)p->got);
+    if (r <= 0) break;
+    p->got += (size_t)r;
+  }
+  return NULL;
+}
+static size_t long_read_plain(int fd, uint8_t *dst, off_t off, size_t want, int nthreads) {
+  long_part part[LONG_READERS];
+  pthread_t th[LONG_READERS];
+  int started[LONG_READERS];
+  const int T = nthreads < 1 ? 1 : nthreads > LONG_READERS ? LONG_READERS : nthreads;
+  const size_t per = ((want + (size_t)T - 1) / (size_t)T + 4095u) & ~(size_t)4095u;
+  int np = 0;
+  for (size_t at = 0; at < want; at += per, np++) {
+    part[np] = (long_part){fd, dst + at, off + (off_t)at, want - at < per ? want - at : per, 0};
+    started[np] = np > 0 && pthread_create(&th[np], NULL, long_part_run, &part[np]) == 0;
+  }
+  size_t have = 0;
+  for (int i = 0; i < np; i++) {
+    if (started[i]) pthread_join(th[i], NULL);
+    else long_part_run(&part[i]); /* the first part, and any part whose thread did not start */
+  }
+  for (int i = 0; i < np; i++) { /* bytes in front of the first short part (the file ended there) */
+    have += part[i].got;
+    if (part[i].got < part[i].n) break;
+  }
+  return have;
+}
+static void sketch_fastq_long(ctx_t *c, const char *path) {
+  for (int k = 0; k < 2; k++)
+    if (!c->long_buf[k] && mk_host_alloc((void **)&c->long_buf[k], LONG_CHUNK) != MK_OK) die("out of memory");
+  const double t_in = now_s();
+  input_t in;
+  if (!open_input(path, &in)) die("mtfastq2koc():%s: %s", path, strerror(errno));
+  struct stat st;
+  const int plain = in.pid == 0 && fstat(fileno(in.f), &st) == 0 && S_ISREG(st.st_mode);
+  mk_engine *e = sketch_engine(c);
+  if (c->t_first_push == 0) c->t_first_push = now_s() - g_t0;
+  unsigned long long pieces = 0, bytes = 0;
+  for (int k = 0;; k ^= 1) {
+    repoison(c->long_buf[k], LONG_CHUNK);
+    size_t have = 0, r;
+    if (plain) have = long_read_plain(fileno(in.f), c->long_buf[k], (off_t)bytes, LONG_CHUNK, c->nthreads);
+    else while (have < LONG_CHUNK && (r = fread(c->long_buf[k] + have, 1, LONG_CHUNK - have, in.f)) > 0) have += r;
+    if (have == 0) break;
+    CHECK(e, mk_sketch_push_fastq_long(e, c->long_buf[k], have, 0));
+    pieces++; bytes += have;
+    if (have < LONG_CHUNK) break;
+  }
+  CHECK(e, mk_sketch_push_fastq_long(e, NULL, 0, 1));
+  close_input(&in);
+  c->t_last_push = now_s() - g_t0;
+  if (g_opt.timing)
+    printf("{\"input\": \"%s\", \"route\": \"long-reads\", \"source\": \"%s\", \"pieces\": %llu, \"text_bytes\": %llu, \"route_total_s\": %.4f}\n", path,
+           is_compressed(path) ? "zcat" : "file", pieces, bytes, now_s() - t_in);
+}
 static void sketch_fastq(ctx_t *c, const char *path) {
+  if (g_opt.long_reads && !c->occ) { sketch_fastq_long(c, path); return; }
   if (sketch_fastq_mapped(c, path)) return;
   if (sketch_fastq_bgzf(c, path)) return;
   if (sketch_fastq_gunzip(c, path)) return;
@@ -1660,7 +1730,7 @@ int run_stage1(int stage2_after) {
    * engines beside a working one takes 0.04 to 1 s each, two pay, more do not.  --engines 1 turns it off */
   if (o->engines_per_gpu < 0 || o->engines_per_gpu > MAX_ENGINES_PER_GPU) die("--engines takes 1..%d", MAX_ENGINES_PER_GPU);
   plan_batches(s, &B);
-  const int n_engines = s->n_engines = (!s->use_batch && !shard_files && ndev <= 1 && files->n >= 8 && !fu->on) ? (o->engines_per_gpu ? o->engines_per_gpu : MK_DEFAULT_ENGINES) : 1;
+  const int n_engines = s->n_engines = (!s->use_batch && !shard_files && ndev <= 1 && files->n >= 8 && !fu->on && !o->long_reads) ? (o->engines_per_gpu ? o->engines_per_gpu : MK_DEFAULT_ENGINES) : 1;
   if (n_engines > 1) {
     s->extra.P = P; s->extra.device = ndev ? o->devs[0] : device; s->extra.want = n_engines - 1;
     if (pthread_create(&s->extra.th, NULL, extra_engines_run, &s->extra) != 0) die("cannot start a thread: %s", strerror(errno));
@@ -1685,7 +1755,7 @@ int run_stage1(int stage2_after) {
   int rc = fu->on ? MK_OK : mk_sketchdir_open(o->outdir, P, koc_dir, files->n, &s->sd);
   if (rc != MK_OK) die("cannot create sketch directory %s (%d)", o->outdir, rc);
   s->jo = (job_opts){files, P, o->abundance, o->uniq, first_nonfq, o->kmerocrs, o->kmerqlty, s->nthreads, s->quiet, &s->pf, 0};
-  if (files->n > 1 && s->nthreads > 1 && !s->use_batch) start_prefetch(s, first_nonfq);
+  if (files->n > 1 && s->nthreads > 1 && !s->use_batch && !o->long_reads) start_prefetch(s, first_nonfq); /* (its workers frame FASTQ files into rows) */
   if (first_nonfq < files->n && o->abundance) printf("Warning: close abundance mode (-A) since non-fastq file input.\n");
   if (s->use_batch) run_batches(s, &B);
   else if (shard_files) run_sharded(s);

@@ -9,6 +9,7 @@
 #include "mk_poison.hip.h"
 #include "mk_kernels.hip.h"
 #include "mk_stream.hip.h"
+#include "mk_fastq_long.hip.h"
 #include "mk_batch.hip.h"
 #include "mk_gz.hip.h"
 #include "mk_packed.hip.h"
@@ -138,6 +139,12 @@ struct mk_engine {
   uint64_t fa_rows_done = 0; /* virtual rows scanned so far in this sketch = ordinal of the next one */
   bool fa_used = false, fa_final = false;
   uint32_t fa_pitch = 0;     /* this sketch's row step (0: not chosen yet) */
+  /* mk_sketch_push_fastq_long: the same buffers and state; summaries of their own, and the record left open behind the last push */
+  mk_fql_sum *d_fq_sum = nullptr;
+  size_t fq_sum_cap = 0;
+  std::vector<uint8_t> fq_carry; /* text behind the last complete record: goes in front of the next push's text */
+  uint64_t fq_total = 0;         /* bytes in d_text of the push that has not been settled: carry + piece */
+  bool fq_used = false, fq_pending = false; /* fq_pending: a non-final push is queued, its state has not been read back */
 
   /* batches of small inputs (mk_sketch_batch_begin / _end): three contexts, two batches in flight, the third holds the results
    * handed out last */
@@ -327,6 +334,7 @@ extern "C" int mk_engine_destroy(mk_engine *e) {
   if (e->ev_scan_post) hipEventDestroy(e->ev_scan_post);
   if (e->ev_res) hipEventDestroy(e->ev_res);
   hipFree(e->d_text); hipFree(e->d_stream); hipFree(e->d_stream_tmp); hipFree(e->d_fa_sum); hipFree(e->d_fa_state);
+  hipFree(e->d_fq_sum);
   if (e->h_fa_state) hipHostFree(e->h_fa_state);
   for (int i = 0; i < MK_TICKETS; i++) if (e->ev_ticket[i]) hipEventDestroy(e->ev_ticket[i]);
   if (e->h_counters) hipHostFree(e->h_counters);
@@ -670,6 +678,7 @@ static int mk_poison_scratch(mk_engine *e) {
   if (e->d_stream) MK_HIP(e, mk_dev_repoison(e->d_stream, e->stream_cap, s));
   if (e->d_stream_tmp) MK_HIP(e, mk_dev_repoison(e->d_stream_tmp, 8192, s));
   if (e->d_fa_sum) MK_HIP(e, mk_dev_repoison(e->d_fa_sum, e->fa_sum_cap * sizeof(mk_fa_sum), s));
+  if (e->d_fq_sum) MK_HIP(e, mk_dev_repoison(e->d_fq_sum, e->fq_sum_cap * sizeof(mk_fql_sum), s));
   if (e->d_stage[0] && e->copy_stream == e->stream) /* (rows staged for a sketch that was never finished are dropped by the begin) */
     for (int i = 0; i < MK_REGIONS; i++) MK_HIP(e, mk_dev_repoison(e->d_stage[i], e->stage_bytes, s));
   return MK_OK;
@@ -983,6 +992,7 @@ extern "C" int mk_sketch_begin(mk_engine *e, int mode) {
   e->count_queued = false;
   e->D = 0;
   e->fa_used = false; e->fa_final = false; e->fa_tail = 0; e->fa_rows_done = 0; e->fa_pitch = 0;
+  e->fq_used = false; e->fq_pending = false; e->fq_carry.clear(); e->fq_total = 0;
   return MK_OK;
 }
 
@@ -1468,6 +1478,104 @@ extern "C" int mk_sketch_push_stream(mk_engine *e, const uint8_t *text, uint64_t
   e->fa_tail = len > taken * pitch ? len - taken * pitch : 0;
   if (e->fa_tail > 8192) return mk_fail(e, MK_ERR_HIP, "mk_sketch_push_stream: stream tail of %llu bytes", (unsigned long long)e->fa_tail);
   return MK_OK;
+}
+
+/* ---- FASTQ text of any line length straight to the device (mk_sketch_push_fastq_long) --------------------------------
+ * mt_shortreads2koc() with FQ_LEN unbounded (iseq2comem.c:656-720): mk_fastq_long.hip.h keeps the sequence lines of complete records,
+ * one '>' behind each, in the base stream mk_sketch_push_stream uses, and the scan kernel reads the same virtual rows out of it.
+ * A record's bases must not be scanned before its fourth line has come (:673 drops the record otherwise), so the text behind the
+ * last complete record of a push -- the open record -- is not emitted; it is read back and goes in front of the next push's text,
+ * which therefore always starts at a record start.  A non-final push waits for the stream anyway (rows taken, stream tail); with
+ * pinned text that wait is put off to the start of the next call, so the caller fills its next buffer beside this push's kernels. */
+static int mk_fql_settle(mk_engine *e) {
+  if (!e->fq_pending) return MK_OK;
+  e->fq_pending = false;
+  MK_HIP(e, hipStreamSynchronize(e->stream));
+  const uint64_t taken = e->h_fa_state->nrows, len = e->h_fa_state->len, consumed = e->h_fa_state->in_header, total = e->fq_total;
+  e->fa_rows_done += taken;
+  e->fa_tail = len > taken * e->fa_pitch ? len - taken * e->fa_pitch : 0;
+  if (e->fa_tail > 8192) return mk_fail(e, MK_ERR_HIP, "mk_sketch_push_fastq_long: stream tail of %llu bytes", (unsigned long long)e->fa_tail);
+  if (consumed > total || (consumed && consumed <= e->fq_carry.size()))
+    return mk_fail(e, MK_ERR_HIP, "mk_sketch_push_fastq_long: record end at %llu of %llu bytes", (unsigned long long)consumed, (unsigned long long)total);
+  /* d_text holds the old carry and the piece: what lies behind the last record end is the new carry (no record end: all of it) */
+  try { e->fq_carry.resize((size_t)(total - consumed)); } catch (...) { return mk_fail(e, MK_ERR_NOMEM, "mk_sketch_push_fastq_long: %llu bytes for an open record", (unsigned long long)(total - consumed)); }
+  if (total > consumed) {
+    MK_HIP(e, hipMemcpyAsync(e->fq_carry.data(), e->d_text + consumed, (size_t)(total - consumed), hipMemcpyDeviceToHost, e->stream));
+    MK_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  return MK_OK;
+}
+
+static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int final) {
+  const uint64_t c = e->fq_carry.size(), total = c + n;
+  int rc = mk_fa_reserve(e, (size_t)total);
+  if (rc) return rc;
+  const uint64_t nseg = (total + MK_FA_SEG - 1) / MK_FA_SEG;
+  if (nseg > e->fq_sum_cap) {
+    MK_HIP(e, hipStreamSynchronize(e->stream));
+    hipFree(e->d_fq_sum);
+    e->d_fq_sum = nullptr; e->fq_sum_cap = 0;
+    MK_HIP(e, mk_dev_alloc(&e->d_fq_sum, (nseg + nseg / 4 + 256) * sizeof(mk_fql_sum)));
+    e->fq_sum_cap = nseg + nseg / 4 + 256;
+  }
+  if (!e->fa_pitch) e->fa_pitch = (final && total <= MK_FA_SMALL_BYTES) ? MK_FA_PITCH_SMALL : MK_FA_PITCH; /* a whole small text at once */
+  const uint32_t TL = (uint32_t)e->P.TL, pitch = e->fa_pitch, rowlen = pitch + TL - 1u;
+  const uint32_t width = (rowlen + 1u + 15u) & ~15u;
+  e->fa_used = true; e->fq_used = true;
+  bool pinned = true;
+  if (n) {
+    hipPointerAttribute_t attr;
+    pinned = hipPointerGetAttributes(&attr, text) == hipSuccess && attr.type == hipMemoryTypeHost;
+    if (!pinned) (void)hipGetLastError();
+  }
+  if (c) MK_HIP(e, hipMemcpyAsync(e->d_text, e->fq_carry.data(), (size_t)c, hipMemcpyHostToDevice, e->stream));
+  if (n) MK_HIP(e, hipMemcpyAsync(e->d_text + c, text, (size_t)n, hipMemcpyHostToDevice, e->stream));
+  if (c || !pinned) MK_HIP(e, hipStreamSynchronize(e->stream)); /* pageable memory (the carry is): free again when the call returns */
+  if (nseg) hipLaunchKernelGGL(mk_fql_summary_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text, total, e->d_fq_sum);
+  hipLaunchKernelGGL(mk_fql_scan_kernel, dim3(1), dim3(1024), 0, e->stream, e->d_fq_sum, nseg, (const uint8_t *)e->d_text, total, e->d_fa_state,
+                     e->d_stream, pitch, rowlen, TL, final ? 1 : 0);
+  if (nseg) hipLaunchKernelGGL(mk_fql_emit_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text,
+                               (const mk_fql_sum *)e->d_fq_sum, (const mk_fa_state *)e->d_fa_state, e->d_stream, (unsigned long long)e->fa_tail);
+  MK_HIP(e, hipGetLastError());
+  const uint64_t ub_len = e->fa_tail + total; /* rows the launch is sized for: what the stream could hold at most */
+  uint64_t ub_rows = 0;
+  if (final) { if (ub_len >= TL) ub_rows = (ub_len - (TL - 1u) + pitch - 1u) / pitch; }
+  else if (ub_len >= rowlen) ub_rows = (ub_len - rowlen) / pitch + 1u;
+  if (ub_rows) {
+    rc = mk_launch_scan_ex(e, e->d_stream, width, pitch, rowlen, ub_rows, &e->d_fa_state->nrows, e->fa_rows_done);
+    if (rc) return rc;
+  }
+  if (final) { e->fa_final = true; e->fq_carry.clear(); return MK_OK; }
+  hipLaunchKernelGGL(mk_fa_shift_kernel, dim3(8), dim3(1024), 0, e->stream, e->d_stream, e->d_stream_tmp, e->d_fa_state, pitch, 0);
+  hipLaunchKernelGGL(mk_fa_shift_kernel, dim3(8), dim3(1024), 0, e->stream, e->d_stream, e->d_stream_tmp, e->d_fa_state, pitch, 1);
+  MK_HIP(e, hipMemcpyAsync(e->h_fa_state, e->d_fa_state, sizeof(mk_fa_state), hipMemcpyDeviceToHost, e->stream));
+  hipLaunchKernelGGL(mk_fa_shift_done_kernel, dim3(1), dim3(1), 0, e->stream, e->d_fa_state, pitch);
+  MK_HIP(e, hipGetLastError());
+  e->fq_pending = true;
+  e->fq_total = total;
+  return pinned ? MK_OK : mk_fql_settle(e);
+}
+
+extern "C" int mk_sketch_push_fastq_long(mk_engine *e, const uint8_t *text, uint64_t n, int final) {
+  if (!e || (!text && n)) return MK_ERR_ARG;
+  if (!e->begun) return mk_fail(e, MK_ERR_STATE, "push before mk_sketch_begin");
+  if (e->mode != MK_MODE_KOC) return mk_fail(e, MK_ERR_STATE, "mk_sketch_push_fastq_long: for MK_MODE_KOC sketches only");
+  if (e->fa_final) return mk_fail(e, MK_ERR_STATE, "mk_sketch_push_fastq_long: the stream has been closed (final) for this sketch");
+  if (e->fa_used && !e->fq_used) return mk_fail(e, MK_ERR_STATE, "mk_sketch_push_fastq_long: this sketch has taken FASTA text (mk_sketch_push_stream)");
+  if (n >= (1ull << 31)) return mk_fail(e, MK_ERR_ARG, "mk_sketch_push_fastq_long: at most 2^31 - 1 bytes per call");
+  if (e->P.TL + MK_FA_PITCH > 4000u) return mk_fail(e, MK_ERR_ARG, "mk_sketch_push_fastq_long: k-mer too long for the stream rows");
+  MK_HIP(e, hipSetDevice(e->device));
+  { int rc = mk_flush_region(e); if (rc) return rc; }
+  for (;;) {
+    int rc = mk_fql_settle(e);
+    if (rc) return rc;
+    /* open record + piece go through the kernels as one text of less than 2^31 bytes */
+    const uint64_t room = ((1ull << 31) - 1u) - e->fq_carry.size();
+    if (n <= room) return mk_fql_push_piece(e, text, n, final);
+    if (!room) return mk_fail(e, MK_ERR_ARG, "mk_sketch_push_fastq_long: a record of 2^31 bytes or more");
+    if ((rc = mk_fql_push_piece(e, text, room, 0))) return rc;
+    text += room; n -= room;
+  }
 }
 
 /* ---- compaction / partials --------------------------------------------------------------------------- */

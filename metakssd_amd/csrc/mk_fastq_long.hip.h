@@ -1,0 +1,201 @@
+/*
+ * mk_fastq_long.hip.h -- device side of mk_sketch_push_fastq_long(): FASTQ text of any line length -> base stream (gfx950, wave64).
+ *
+ * mt_shortreads2koc() (iseq2comem.c:672-720) takes four fgets() lines a record and walks the second one up to its '\n'; a byte that
+ * is no base resets the k-mer window (:682-690).  Its FQ_LEN (:656) cuts lines of 4 095 characters and more and mis-frames the file
+ * from there on; this route is the same loop with FQ_LEN unbounded.  It is the FASTQ flavour of mk_stream.hip.h -- the same three
+ * kernels with another rule for which bytes stay:
+ *     role of a byte : (number of '\n' in front of it) mod 4 -- 0 header, 1 sequence, 2 '+' line, 3 quality
+ *     kept           : exactly the bytes of role 1, whatever they are ('\r', 'N', bytes >= 0x80: the scan kernel resets on them as the
+ *                      reference's loop does); the '\n' that ends the line goes in as ONE '>' (no base and no row end: the window
+ *                      resets between two reads, as `base = 1` does at the top of the per-read loop)
+ *     dropped        : every byte of the other three lines, whatever it is
+ * The state is a newline count, so a segment's summary is {its newlines, bytes kept for each of the four entry roles}, and composing
+ * the summaries is two plain prefix sums: newlines (-> entry role of every segment), then the kept bytes for that role.
+ *
+ * Record rule (:673): a record counts when its fourth fgets() gives at least one byte.  The text of one push always starts at a record
+ * start (the host carries the open record in front of the next push's text, mk_engine.hip), so with N newlines in the push the last
+ * record ends behind newline number 4 * (N / 4); the scan kernel finds that byte (`consumed`), the emit kernel stops there.  The
+ * final push also takes a last record whose quality line has bytes but no '\n' (N mod 4 == 3, last byte no '\n').
+ *   mk_fql_summary_kernel  one wave per segment of MK_FA_SEG bytes
+ *   mk_fql_scan_kernel     one workgroup: prefix sums, the cut, stream length and row count (as mk_fa_scan_kernel)
+ *   mk_fql_emit_kernel     the same walk with the entry role known: kept bytes to stream[offset ..], up to the cut
+ */
+#pragma once
+#include "mk_stream.hip.h"
+
+struct mk_fql_sum { /* per segment */
+  uint32_t cnt[4]; /* bytes kept when the segment is entered in role 0..3 */
+  uint32_t nl;     /* newlines in the segment */
+  uint32_t nlpre;  /* scan: newlines in front of the segment (its entry role is nlpre & 3) */
+  uint32_t off;    /* scan: output offset of the segment, relative to the stream length before this push */
+  uint32_t pad;
+};
+
+/* one 64-byte step entered in role `role` (wave-uniform): the lanes whose bytes are kept; role := the role behind the step */
+__device__ __forceinline__ uint64_t mk_fql_step(uint8_t ch, bool valid, uint32_t lane, uint32_t &role) {
+  const uint64_t nl = __ballot(valid && ch == '\n');
+  if (nl == 0ull) return role == 1u ? __ballot(valid) : 0ull; /* inside one line: nearly every step of a long read */
+  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull; /* lanes in front of this one */
+  const uint32_t mine = (role + (uint32_t)__popcll(nl & below)) & 3u;
+  role = (role + (uint32_t)__popcll(nl)) & 3u;
+  return __ballot(valid && mine == 1u);
+}
+
+__global__ void __launch_bounds__(256) mk_fql_summary_kernel(const uint8_t *text, uint64_t n, mk_fql_sum *sum) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t segi = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint64_t lo = segi * MK_FA_SEG;
+  if (lo >= n) return;
+  const uint64_t hi = lo + MK_FA_SEG < n ? lo + MK_FA_SEG : n;
+  __shared__ uint4 seg_lds[MK_FA_WAVES][64];
+  const uint8_t *seg = mk_fa_stage(text, lo, lane, seg_lds[threadIdx.x >> 6]);
+  const uint32_t len = (uint32_t)(hi - lo);
+  const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;
+  uint32_t c[4] = {0u, 0u, 0u, 0u}, nls = 0u;
+#pragma unroll
+  for (uint32_t j = 0; j < MK_FA_SEG / 64u; j++) {
+    if (64u * j >= len) break;
+    const bool valid = 64u * j + lane < len;
+    const uint8_t ch = seg[64u * j + lane];
+    const uint64_t nl = __ballot(valid && ch == '\n');
+    /* q: newlines of the segment in front of this byte, mod 4; entered in role r the byte has role (r + q) & 3, kept when that is 1 */
+    const uint32_t q = (nls + (uint32_t)__popcll(nl & below)) & 3u;
+    if (nl == 0ull) { /* one line: q is the same in every lane */
+      const uint32_t all = (uint32_t)__popcll(__ballot(valid));
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; r++) c[r] += ((r + q) & 3u) == 1u ? all : 0u;
+    } else {
+#pragma unroll
+      for (uint32_t r = 0; r < 4u; r++) c[r] += (uint32_t)__popcll(__ballot(valid && ((r + q) & 3u) == 1u));
+    }
+    nls += (uint32_t)__popcll(nl);
+  }
+  if (lane == 0) {
+    mk_fql_sum r;
+    r.cnt[0] = c[0]; r.cnt[1] = c[1]; r.cnt[2] = c[2]; r.cnt[3] = c[3];
+    r.nl = nls; r.nlpre = 0u; r.off = 0u; r.pad = 0u;
+    sum[segi] = r;
+  }
+}
+
+/* exclusive prefix sum over the workgroup's 1024 threads (all of them call); total := the sum of all */
+__device__ __forceinline__ uint32_t mk_fql_block_scan(uint32_t v, uint32_t &total) {
+  __shared__ uint32_t wsum[16];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (uint32_t o = 1; o < 64u; o <<= 1) {
+    const uint32_t p = __shfl_up(inc, o);
+    if (lane >= o) inc += p;
+  }
+  __syncthreads(); /* (the call before this one has been read) */
+  if (lane == 63u) wsum[wave] = inc;
+  __syncthreads();
+  uint32_t base = 0u, all = 0u;
+  for (uint32_t w = 0; w < 16u; w++) { if (w < wave) base += wsum[w]; all += wsum[w]; }
+  total = all;
+  return base + inc - v;
+}
+
+/* One workgroup of 1024 threads.  The push's text starts at a record start (role 0).  st->in_header := `consumed`, the text offset
+ * behind the last byte of the last complete record (0: none); st->len, st->nrows as mk_fa_scan_kernel sets them, for the kept bytes
+ * in front of that offset only. */
+__global__ void __launch_bounds__(1024) mk_fql_scan_kernel(mk_fql_sum *sum, uint64_t nseg, const uint8_t *text, uint64_t n, mk_fa_state *st,
+                                                          uint8_t *stream, uint32_t pitch, uint32_t rowlen, uint32_t TL, int final) {
+  __shared__ uint32_t cut_seg, cut_pos, cut_kept;
+  __shared__ uint4 seg_lds[64];
+  /* newlines in front of every segment */
+  uint32_t carry = 0u;
+  for (uint64_t base = 0; base < nseg; base += 1024u) {
+    const uint64_t i = base + threadIdx.x;
+    uint32_t total;
+    const uint32_t ex = mk_fql_block_scan(i < nseg ? sum[i].nl : 0u, total);
+    if (i < nseg) sum[i].nlpre = carry + ex;
+    carry += total;
+  }
+  const uint32_t N = carry;
+  /* the last record: ends behind newline number want (counted from 1), or with the text */
+  const bool open_end = final && n && (N & 3u) == 3u && text[n - 1] != (uint8_t)'\n';
+  const uint32_t want = N & ~3u;
+  if (threadIdx.x == 0) { cut_seg = 0xFFFFFFFFu; cut_pos = 0u; cut_kept = 0u; }
+  __syncthreads();
+  /* output offset of every segment; the segment that holds the cut */
+  carry = 0u;
+  for (uint64_t base = 0; base < nseg; base += 1024u) {
+    const uint64_t i = base + threadIdx.x;
+    uint32_t mine = 0u, pre = 0u, nl = 0u;
+    if (i < nseg) { pre = sum[i].nlpre; nl = sum[i].nl; mine = sum[i].cnt[pre & 3u]; }
+    uint32_t total;
+    const uint32_t ex = mk_fql_block_scan(mine, total);
+    if (i < nseg) {
+      sum[i].off = carry + ex;
+      if (!open_end && want && pre < want && want <= pre + nl) cut_seg = (uint32_t)i; /* exactly one segment */
+    }
+    carry += total;
+  }
+  const uint32_t K = carry;
+  __syncthreads();
+  /* one wave walks that segment up to its newline number want - nlpre: where it is, and what is kept up to and with it */
+  if (threadIdx.x < 64u && cut_seg != 0xFFFFFFFFu) {
+    const uint32_t lane = threadIdx.x;
+    const uint64_t lo = (uint64_t)cut_seg * MK_FA_SEG;
+    const uint32_t len = (uint32_t)(lo + MK_FA_SEG < n ? MK_FA_SEG : n - lo);
+    uint32_t left = want - sum[cut_seg].nlpre; /* newlines still to pass, the wanted one included */
+    uint32_t role = sum[cut_seg].nlpre & 3u, kept = 0u;
+    const uint8_t *seg = mk_fa_stage(text, lo, lane, seg_lds);
+    for (uint32_t j = 0; j < MK_FA_SEG / 64u; j++) {
+      if (64u * j >= len) break;
+      const bool valid = 64u * j + lane < len;
+      const uint8_t ch = seg[64u * j + lane];
+      uint64_t nl = __ballot(valid && ch == '\n');
+      const uint64_t keep = mk_fql_step(ch, valid, lane, role);
+      const uint32_t here = (uint32_t)__popcll(nl);
+      if (here < left) { left -= here; kept += (uint32_t)__popcll(keep); continue; }
+      for (uint32_t t = 1; t < left; t++) nl &= nl - 1ull; /* drop the newlines in front of the wanted one */
+      const uint32_t at = (uint32_t)__builtin_ctzll(nl);
+      kept += (uint32_t)__popcll(keep & ((2ull << at) - 1ull));
+      if (lane == 0) { cut_pos = 64u * j + at + 1u; cut_kept = kept; }
+      break;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long consumed = 0ull, kept = 0ull;
+    if (open_end) { consumed = n; kept = K; }
+    else if (cut_seg != 0xFFFFFFFFu) { consumed = (unsigned long long)cut_seg * MK_FA_SEG + cut_pos; kept = (unsigned long long)sum[cut_seg].off + cut_kept; }
+    const unsigned long long len = st->len + kept;
+    st->len = len;
+    st->in_header = (uint32_t)consumed;
+    unsigned long long rows = 0;
+    if (final) {
+      if (len >= TL) rows = (len - (TL - 1u) + pitch - 1u) / pitch; /* every row with a complete k-mer in it */
+      stream[len] = (uint8_t)'\n'; /* the last row ends here */
+    } else if (len >= rowlen) rows = (len - rowlen) / pitch + 1u; /* complete rows only */
+    st->nrows = rows;
+  }
+}
+
+/* the text once more with every segment's entry role and offset known: bytes of sequence lines in front of the cut go to the stream */
+__global__ void __launch_bounds__(256) mk_fql_emit_kernel(const uint8_t *text, const mk_fql_sum *sum, const mk_fa_state *st, uint8_t *stream,
+                                                         unsigned long long stream_len_before) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t segi = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint64_t lo = segi * MK_FA_SEG, n = st->in_header; /* (this push's `consumed`: mk_fql_scan_kernel ran in front of this kernel) */
+  if (lo >= n) return;
+  const uint64_t hi = lo + MK_FA_SEG < n ? lo + MK_FA_SEG : n;
+  __shared__ uint4 seg_lds[MK_FA_WAVES][64];
+  const uint8_t *seg = mk_fa_stage(text, lo, lane, seg_lds[threadIdx.x >> 6]);
+  const uint32_t len = (uint32_t)(hi - lo);
+  uint32_t role = sum[segi].nlpre & 3u;
+  uint64_t off = stream_len_before + sum[segi].off;
+#pragma unroll
+  for (uint32_t j = 0; j < MK_FA_SEG / 64u; j++) {
+    if (64u * j >= len) break;
+    const bool valid = 64u * j + lane < len;
+    const uint8_t ch = seg[64u * j + lane];
+    const uint64_t keep = mk_fql_step(ch, valid, lane, role);
+    if ((keep >> lane) & 1ull) stream[off + mk_mbcnt(keep)] = ch == (uint8_t)'\n' ? (uint8_t)'>' : ch;
+    off += (uint64_t)__popcll(keep);
+  }
+}
