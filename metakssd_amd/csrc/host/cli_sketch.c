@@ -481,6 +481,15 @@ static void report_route(const char *path, const char *route, const mk_bgzf_stat
          bs ? (unsigned long long)bs->text_bytes : 0ull, bs ? (unsigned long long)bs->rows : 0ull, bs ? bs->inflate_ms : 0.0, bs ? bs->frame_ms : 0.0,
          bs ? bs->t_scan_s : 0.0, bs ? bs->t_read_s : 0.0, bs ? bs->t_total_s : 0.0, fb);
 }
+/* the device route gave an input up: what it pushed is finished and dropped, the next push begins anew, --timing names the reason */
+static void drop_pushed_and_fall_back(ctx_t *c, mk_engine *e, const char *why) {
+  mk_result dropped;
+  const int frc = mk_sketch_finish(e, &dropped);
+  if (frc != MK_OK && frc != MK_ERR_CROWDED) die("mk_sketch_finish failed (%d): %s", frc, mk_last_error(e));
+  if (frc == MK_OK) mk_result_release(e, &dropped);
+  c->begun = 0;
+  g_gz_fallback = why;
+}
 /* a .gz that is a BGZF chain from its first byte to its last (mk_bgzf_scan) is inflated, checked and framed on the device; 0: not
  * such a file, the caller goes on with `zcat -fc`, with today's behaviour and messages.  The -n / -Q reader (c->occ) takes this
  * route only with --device-inflate, and a file with a line of 4095+ characters -- which fastq2co() reads (iseq2comem.c:319,343) and
@@ -509,11 +518,7 @@ static int sketch_fastq_bgzf(ctx_t *c, const char *path) {
   if (rc == MK_ERR_FORMAT && bs.bad_block >= 0)
     die("%s: BGZF block %lld is damaged (%s): the input was not read completely", path, (long long)bs.bad_block, mk_inflate_status_text(bs.bad_status));
   if (rc == MK_ERR_FORMAT && c->occ) {
-    mk_result dropped;
-    const int frc = mk_sketch_finish(e, &dropped); /* rows of earlier chunks: finished and dropped, the next push begins anew */
-    if (frc != MK_OK && frc != MK_ERR_CROWDED) die("mk_sketch_finish failed (%d): %s", frc, mk_last_error(e));
-    c->begun = 0;
-    g_gz_fallback = "long line";
+    drop_pushed_and_fall_back(c, e, "long line");
     return 0;
   }
   if (rc == MK_ERR_FORMAT)
@@ -544,12 +549,7 @@ static int sketch_fastq_gunzip(ctx_t *c, const char *path) {
                         : mk_sketch_push_gzip(e, fd, (size_t)st.st_size, &g_opt.gunzip_opts, c->next_ordinal, &gs);
   close(fd);
   if (rc == MK_ERR_FORMAT) {
-    mk_result dropped;
-    const int frc = mk_sketch_finish(e, &dropped); /* rows pushed before the status showed: finished and dropped, the next push begins anew */
-    if (frc != MK_OK && frc != MK_ERR_CROWDED) die("mk_sketch_finish failed (%d): %s", frc, mk_last_error(e));
-    if (frc == MK_OK) mk_result_release(e, &dropped);
-    c->begun = 0;
-    g_gz_fallback = gs.bad_status ? mk_gunzip_status_text(gs.bad_status) : "long line";
+    drop_pushed_and_fall_back(c, e, gs.bad_status ? mk_gunzip_status_text(gs.bad_status) : "long line");
     return 0;
   }
   if (rc != MK_OK) die("%s failed (%d): %s", c->occ ? "mk_sketch_push_gzip_q" : "mk_sketch_push_gzip", rc, mk_bgzf_last_error());

@@ -478,21 +478,9 @@ struct mk_gun_result {
   double find_ms = 0, decode_ms = 0, resolve_ms = 0, t_read_s = 0;
 };
 
-template <class T>
-static hipError_t mk_gun_grow(T **p, uint64_t *cap, uint64_t need, bool pinned = false) {
-  if (need == 0) need = 1;
-  if (*p && need <= *cap) return hipSuccess;
-  if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); }
-  *p = nullptr; *cap = 0;
-  const uint64_t c = need + need / 8 + 256;
-  const hipError_t r = pinned ? mk_pin_alloc(p, c * sizeof(T), hipHostMallocDefault) : mk_dev_alloc(p, c * sizeof(T));
-  if (r == hipSuccess) *cap = c;
-  return r;
-}
-
 struct mk_gun_run { /* everything the stream decode allocates, released on every way out */
   hipStream_t S = nullptr, copy = nullptr;
-  uint8_t *h_stage[2] = {nullptr, nullptr}, *d_comp = nullptr, *d_win = nullptr, *d_wcarry = nullptr, *d_text = nullptr;
+  uint8_t *h_stage[2] = {nullptr, nullptr}, *d_comp = nullptr, *d_win = nullptr, *d_wcarry = nullptr, *d_text = nullptr, *d_fcarry = nullptr; /* d_fcarry: mk_push_gzip's, FASTQ text between batches */
   uint64_t *d_cand = nullptr, *h_cand = nullptr;
   mk_gun_piece *d_pieces = nullptr, *h_pieces = nullptr;
   uint16_t *d_syms = nullptr;
@@ -505,7 +493,7 @@ struct mk_gun_run { /* everything the stream decode allocates, released on every
   char err[256] = {0};
   ~mk_gun_run() {
     for (int s = 0; s < 2; s++) { if (h_stage[s]) (void)hipHostFree(h_stage[s]); if (ev_up[s]) (void)hipEventDestroy(ev_up[s]); }
-    void *dev[] = {d_comp, d_win, d_wcarry, d_text, d_cand, d_pieces, d_syms, d_crctab, d_crcwork, d_mems, d_dense};
+    void *dev[] = {d_comp, d_win, d_wcarry, d_text, d_fcarry, d_cand, d_pieces, d_syms, d_crctab, d_crcwork, d_mems, d_dense};
     for (void *p : dev) (void)hipFree(p);
     void *pin[] = {h_cand, h_pieces, h_crctab, h_crc, h_dense};
     for (void *p : pin) if (p) (void)hipHostFree(p);
@@ -597,8 +585,8 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     const uint32_t n = (uint32_t)(c1 - c0);
     int rc = ensure_uploaded(shift + c1 * S + ahead); /* (a block header that starts in the span's last bits ends within 2.3 KB) */
     if (rc) return rc;
-    MK_GUN_HIP(mk_gun_grow(&R.d_cand, &R.cand_cap, n));
-    MK_GUN_HIP(mk_gun_grow(&R.h_cand, &R.hcand_cap, n, true));
+    MK_GUN_HIP(mk_grow(&R.d_cand, &R.cand_cap, n, false));
+    MK_GUN_HIP(mk_grow(&R.h_cand, &R.hcand_cap, n, true));
     MK_GUN_HIP(hipEventRecord(R.ev_t[0], R.S));
     hipLaunchKernelGGL(members ? mk_gun_find_kernel<true> : mk_gun_find_kernel<false>, dim3((n + MK_INFL_WAVES - 1) / MK_INFL_WAVES), dim3(64 * MK_INFL_WAVES), 0, R.S,
                        (const uint8_t *)R.d_comp, shift, pay_len, S, c0, n, R.d_cand);
@@ -632,8 +620,8 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     while (idx_end == starts.size() && found < NB) { rc = find_batch(found++); if (rc) return rc; } /* where the batch's last piece ends */
     const uint32_t np = (uint32_t)(idx_end - idx);
     const bool final = idx_end == starts.size();
-    MK_GUN_HIP(mk_gun_grow(&R.h_pieces, &R.hpieces_cap, np, true));
-    MK_GUN_HIP(mk_gun_grow(&R.d_pieces, &R.pieces_cap, np));
+    MK_GUN_HIP(mk_grow(&R.h_pieces, &R.hpieces_cap, np, true));
+    MK_GUN_HIP(mk_grow(&R.d_pieces, &R.pieces_cap, np, false));
     uint64_t nsyms = 0, nslots = 0;
     for (uint32_t k = 0; k < np; k++) {
       mk_gun_piece &P = R.h_pieces[k];
@@ -658,9 +646,9 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
         nslots += P.mem_cap;
       }
     }
-    if (members) MK_GUN_HIP(mk_gun_grow(&R.d_mems, &R.mems_cap, nslots));
-    MK_GUN_HIP(mk_gun_grow(&R.d_syms, &R.syms_cap, nsyms));
-    MK_GUN_HIP(mk_gun_grow(&R.d_win, &R.win_cap, ((uint64_t)np + 1u) * MK_GUN_WINDOW));
+    if (members) MK_GUN_HIP(mk_grow(&R.d_mems, &R.mems_cap, nslots, false));
+    MK_GUN_HIP(mk_grow(&R.d_syms, &R.syms_cap, nsyms, false));
+    MK_GUN_HIP(mk_grow(&R.d_win, &R.win_cap, ((uint64_t)np + 1u) * MK_GUN_WINDOW, false));
     rc = ensure_uploaded(R.h_pieces[np - 1].end == MK_GUN_NONE ? total : shift + (R.h_pieces[np - 1].end >> 3) + 4096u);
     if (rc) return rc;
     MK_GUN_HIP(hipMemcpyAsync(R.d_pieces, R.h_pieces, (size_t)np * sizeof(mk_gun_piece), hipMemcpyHostToDevice, R.S));
@@ -694,11 +682,11 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
       nrec += P.nmem;
     }
     /* chain, resolve, CRC */
-    MK_GUN_HIP(mk_gun_grow(&R.d_text, &R.text_cap, mk_fq_buf_bytes(MK_FQ_CARRY + ntext)));
+    MK_GUN_HIP(mk_grow(&R.d_text, &R.text_cap, mk_fq_buf_bytes(MK_FQ_CARRY + ntext), false));
     MK_GUN_HIP(hipMemcpyAsync(R.d_pieces, R.h_pieces, (size_t)np * sizeof(mk_gun_piece), hipMemcpyHostToDevice, R.S));
     if (nrec) { /* the members that ended in this batch: their ends in its text, their trailers */
-      MK_GUN_HIP(mk_gun_grow(&R.d_dense, &R.dense_cap, nrec));
-      MK_GUN_HIP(mk_gun_grow(&R.h_dense, &R.hdense_cap, nrec, true));
+      MK_GUN_HIP(mk_grow(&R.d_dense, &R.dense_cap, nrec, false));
+      MK_GUN_HIP(mk_grow(&R.h_dense, &R.hdense_cap, nrec, true));
       hipLaunchKernelGGL(mk_gun_members_kernel, dim3(np), dim3(64), 0, R.S, (const mk_gun_piece *)R.d_pieces, (const mk_gun_member *)R.d_mems, R.d_dense);
       MK_GUN_HIP(hipGetLastError());
       MK_GUN_HIP(hipMemcpyAsync(R.h_dense, R.d_dense, (size_t)nrec * sizeof(mk_gun_member), hipMemcpyDeviceToHost, R.S));
@@ -731,8 +719,8 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     uint32_t nslices = 0;
     if (nseg) {
       const size_t tab_bytes = mk_gz_table_bytes(nseg);
-      MK_GUN_HIP(mk_gun_grow(&R.h_crctab, &R.hcrctab_cap, tab_bytes, true));
-      MK_GUN_HIP(mk_gun_grow(&R.d_crctab, &R.crctab_cap, tab_bytes));
+      MK_GUN_HIP(mk_grow(&R.h_crctab, &R.hcrctab_cap, tab_bytes, true));
+      MK_GUN_HIP(mk_grow(&R.d_crctab, &R.crctab_cap, tab_bytes, false));
       mk_infl_blk *tab = (mk_infl_blk *)R.h_crctab;
       uint32_t *slice0s = (uint32_t *)(R.h_crctab + mk_gz_slice0_at(nseg));
       uint64_t at = 0;
@@ -745,8 +733,8 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
       }
       slice0s[nseg] = nslices;
       /* the work words: status[nseg] (zeros) | crc[nseg] | slice registers[nslices] */
-      MK_GUN_HIP(mk_gun_grow(&R.d_crcwork, &R.crcwork_cap, 2u * (uint64_t)nseg + nslices));
-      MK_GUN_HIP(mk_gun_grow(&R.h_crc, &R.hcrc_cap, nseg, true));
+      MK_GUN_HIP(mk_grow(&R.d_crcwork, &R.crcwork_cap, 2u * (uint64_t)nseg + nslices, false));
+      MK_GUN_HIP(mk_grow(&R.h_crc, &R.hcrc_cap, nseg, true));
       MK_GUN_HIP(hipMemcpyAsync(R.d_crctab, R.h_crctab, tab_bytes, hipMemcpyHostToDevice, R.S));
       MK_GUN_HIP(hipMemsetAsync(R.d_crcwork, 0, (size_t)nseg * sizeof(uint32_t), R.S));
       const mk_infl_blk *d_tab = (const mk_infl_blk *)R.d_crctab;
@@ -838,8 +826,7 @@ extern "C" int mk_inflate_stream_members(mk_inflate *h, uint64_t *members) {
 }
 
 /* both readers' route: occ == false is mk_fastq_frame's rule (-A), occ == true mk_fastq_frame_q's (quality mask qmin), one row a
- * record.  What the second adds to the sink: d_qinfo, two words per record a slice can hold; the file's record count (stats.rows),
- * which decides the first-record exception -- it can only arise in the last slice of the last batch, whose text [t0, e1) is then the
+ * record.  What the second needs from the sink: the file's record count (stats.rows), which decides the first-record exception -- it can only arise in the last slice of the last batch, whose text [t0, e1) is then the
  * whole file: everything in front of it went through the carry, possibly in front of an empty batch. */
 static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, bool occ, int32_t qmin, uint64_t first_ordinal, mk_gunzip_stats *st) {
   if (!e || fd < 0) return MK_ERR_ARG;
@@ -856,32 +843,15 @@ static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts 
   int device = 0;
   rc = mk_engine_get_stream(e, &sp, &device);
   if (rc) return rc;
-  struct frame_bufs { /* the framing's own buffers */
-    uint8_t *d_rows = nullptr, *d_carry = nullptr;
-    uint32_t *d_tile_cnt = nullptr, *d_tile_last = nullptr, *d_qinfo = nullptr;
-    mk_fq_res *d_res = nullptr, *h_res = nullptr;
-    uint64_t rows_cap = 0, qinfo_cap = 0; /* bytes, words */
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~frame_bufs() {
-      (void)hipFree(d_rows); (void)hipFree(d_carry); (void)hipFree(d_tile_cnt); (void)hipFree(d_tile_last); (void)hipFree(d_qinfo); (void)hipFree(d_res);
-      if (h_res) (void)hipHostFree(h_res);
-      for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-    }
-  } F;
+  mk_fq_framer F;
   mk_gun_run R;
   R.S = (hipStream_t)sp;
   hipStream_t S = R.S;
   MK_GUN_HIP(hipSetDevice(device));
-  const uint32_t max_tiles = mk_fq_ntiles((uint32_t)(MK_FQ_CARRY + MK_GUN_SLICE));
-  MK_GUN_HIP(mk_dev_alloc(&F.d_carry, (size_t)MK_FQ_CARRY));
-  MK_GUN_HIP(mk_dev_alloc(&F.d_tile_cnt, (size_t)max_tiles * sizeof(uint32_t)));
-  MK_GUN_HIP(mk_dev_alloc(&F.d_tile_last, (size_t)max_tiles * sizeof(uint32_t)));
-  MK_GUN_HIP(mk_dev_alloc(&F.d_res, sizeof(mk_fq_res)));
-  MK_GUN_HIP(mk_pin_alloc(&F.h_res, sizeof(mk_fq_res), hipHostMallocDefault));
-  for (int k = 0; k < 2; k++) MK_GUN_HIP(hipEventCreate(&F.ev[k]));
+  MK_GUN_HIP(F.setup(occ, qmin));
+  MK_GUN_HIP(mk_dev_alloc(&R.d_fcarry, (size_t)MK_FQ_CARRY));
 
-  uint32_t carry = 0; /* bytes behind the last complete record, kept in d_carry between batches */
-  uint64_t ordinal = first_ordinal;
+  uint32_t carry = 0; /* bytes behind the last complete record, kept in R.d_fcarry between batches */
   bool long_line = false;
   auto read = [&](uint64_t off, uint64_t n, uint8_t *dst) -> int {
     for (uint64_t got = 0; got < n;) {
@@ -891,28 +861,16 @@ static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts 
     }
     return MK_OK;
   };
+  mk_fq_handed out{};
+  auto push = [&](const uint8_t *d_rows, uint32_t stride, uint32_t nrows) -> int {
+    return mk_sketch_push_reads_device(e, d_rows, stride, nrows, first_ordinal + stats.rows + out.rows);
+  };
   auto sink = [&](uint8_t *d_text, uint64_t n, bool final_batch) -> int {
     if (n == 0 && !final_batch) return MK_OK;
-    const uint32_t qcap = mk_fq_qcap(MK_FQ_CARRY + std::min<uint64_t>(n, MK_GUN_SLICE)); /* records a slice with its carry can hold */
-    { /* rows of one slice at most (a row is a line of the text, padded); occ: two words per possible record of a slice */
-      const uint64_t need = std::max<uint64_t>(std::min<uint64_t>(n, MK_GUN_SLICE) + MK_FQ_CARRY, (uint64_t)8 << 20) + 4096u;
-      const uint64_t qneed = occ ? 2u * (uint64_t)qcap : 0u;
-      if (need > F.rows_cap || qneed > F.qinfo_cap) MK_GUN_HIP(hipStreamSynchronize(S));
-      if (need > F.rows_cap) {
-        (void)hipFree(F.d_rows);
-        F.d_rows = nullptr; F.rows_cap = 0;
-        MK_GUN_HIP(mk_dev_alloc(&F.d_rows, need));
-        F.rows_cap = need;
-      }
-      if (qneed > F.qinfo_cap) {
-        (void)hipFree(F.d_qinfo);
-        F.d_qinfo = nullptr; F.qinfo_cap = 0;
-        MK_GUN_HIP(mk_dev_alloc(&F.d_qinfo, qneed * sizeof(uint32_t)));
-        F.qinfo_cap = qneed;
-      }
-    }
+    const uint64_t text_end = MK_FQ_CARRY + std::min<uint64_t>(n, MK_GUN_SLICE); /* a slice with its carry; its rows are lines of the text, padded */
+    MK_GUN_HIP(F.reserve(S, text_end, std::max<uint64_t>(text_end, (uint64_t)8 << 20) + 4096u));
     if (carry) {
-      hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)F.d_carry, 0u, d_text, MK_FQ_CARRY - carry, carry);
+      hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)R.d_fcarry, 0u, d_text, MK_FQ_CARRY - carry, carry);
       MK_GUN_HIP(hipGetLastError());
     }
     uint64_t off = 0;
@@ -920,45 +878,21 @@ static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts 
       const uint32_t sl = (uint32_t)std::min<uint64_t>(MK_GUN_SLICE, n - off);
       const int final = final_batch && off + sl == n;
       uint8_t *base = d_text + off;
-      const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + sl, nn = e1 - t0;
-      MK_GUN_HIP(hipEventRecord(F.ev[0], S));
-      if (occ) MK_GUN_HIP(mk_launch_frame_count_q(S, base, t0, e1, final, F.d_tile_cnt, F.d_tile_last, nullptr, 0, F.d_res, F.d_qinfo, qcap));
-      else MK_GUN_HIP(mk_launch_frame_count(S, base, t0, e1, final, F.d_tile_cnt, F.d_tile_last, nullptr, 0, F.d_res));
-      MK_GUN_HIP(hipEventRecord(F.ev[1], S));
-      MK_GUN_HIP(hipMemcpyAsync(F.h_res, F.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
-      MK_GUN_HIP(hipStreamSynchronize(S));
-      mk_fq_res r = *F.h_res;
-      const bool first = occ && mk_fq_res_q(r, nn, final, stats.rows);
-      float ms = 0.f;
-      MK_GUN_HIP(hipEventElapsedTime(&ms, F.ev[0], F.ev[1]));
+      const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + sl;
+      MK_GUN_HIP(F.count(S, base, t0, e1, final, nullptr, 0));
+      mk_fq_chunk q;
+      MK_GUN_HIP(F.result(stats.rows, &q));
+      float ms = 0.f, rows_ms = 0.f; /* frame_ms is the count phase alone on this route */
+      MK_GUN_HIP(F.times(&ms, &rows_ms));
       stats.frame_ms += ms;
-      if (r.maxline >= MK_FQ_LINE_MAX || (!final && nn - r.consumed > MK_FQ_CARRY)) { long_line = true; return MK_ERR_FORMAT; }
-      if (first) { /* no complete record in the whole file: its first one is walked all the same, if it has a sequence line */
-        hipLaunchKernelGGL(mk_fq_first_q_kernel, dim3(1), dim3(64), 0, S, (const uint8_t *)base, t0, e1, qmin, F.d_res, F.d_rows);
-        MK_GUN_HIP(hipGetLastError());
-        MK_GUN_HIP(hipMemcpyAsync(F.h_res, F.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
-        MK_GUN_HIP(hipStreamSynchronize(S));
-        if (F.h_res->nrec) {
-          const int prc = mk_sketch_push_reads_device(e, F.d_rows, mk_fq_stride(F.h_res->maxseq), 1, ordinal);
-          if (prc) { snprintf(R.err, sizeof R.err, "%s", mk_last_error(e)); return prc; }
-          ordinal++;
-          stats.rows++;
-        }
-      }
-      const uint32_t stride = mk_fq_stride(r.maxseq), per = (uint32_t)(F.rows_cap / stride);
-      for (uint32_t r0 = 0; r0 < r.nrec; r0 += per) {
-        const uint32_t r1 = r.nrec - r0 < per ? r.nrec : r0 + per;
-        if (occ) MK_GUN_HIP(mk_launch_frame_rows_q(S, base, t0, e1, F.d_tile_cnt, r0, r1, stride, F.d_qinfo, qmin, F.d_rows));
-        else MK_GUN_HIP(mk_launch_frame_rows(S, base, t0, e1, F.d_tile_cnt, r0, r1, stride, F.d_rows));
-        const int prc = mk_sketch_push_reads_device(e, F.d_rows, stride, r1 - r0, ordinal);
-        if (prc) { snprintf(R.err, sizeof R.err, "%s", mk_last_error(e)); return prc; }
-        ordinal += r1 - r0;
-      }
-      stats.rows += r.nrec;
-      carry = nn - r.consumed;
+      if (q.long_line) { long_line = true; return MK_ERR_FORMAT; }
+      MK_GUN_HIP(F.rows(S, q, push, &out));
+      if (out.push_rc) { snprintf(R.err, sizeof R.err, "%s", mk_last_error(e)); return out.push_rc; }
+      stats.rows += out.rows;
+      carry = out.carry;
       off += sl;
       if (off >= n && carry) { /* behind the batch's last slice: what is left waits for the next batch's text */
-        hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)base, t0 + r.consumed, F.d_carry, 0u, carry);
+        hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)base, t0 + q.r.consumed, R.d_fcarry, 0u, carry);
         MK_GUN_HIP(hipGetLastError());
       }
     } while (off < n);

@@ -235,8 +235,7 @@ extern "C" int mk_inflate_members_split(mk_inflate *h, const uint8_t *comp, size
   /* one upload: the payloads | the member table | the span table of the files */
   const uint64_t tab_at = (comp_bytes + 15u) & ~(uint64_t)15u, ftab_at = tab_at + mk_gz_table_bytes(nmembers);
   const uint64_t stage_bytes = ftab_at + (uint64_t)nmembers * sizeof(mk_gb_file);
-  int rc = mk_infl_grow_pinned(h, &h->h_stage, &h->stage_cap, stage_bytes);
-  if (rc) return rc;
+  MK_INFL_HIP(h, mk_grow(&h->h_stage, &h->stage_cap, stage_bytes, true));
   if (comp_bytes) memcpy(h->h_stage, comp, comp_bytes);
   memset(h->h_stage + comp_bytes, 0, tab_at - comp_bytes);
   mk_infl_blk *tab = (mk_infl_blk *)(h->h_stage + tab_at);
@@ -261,11 +260,10 @@ extern "C" int mk_inflate_members_split(mk_inflate *h, const uint8_t *comp, size
   } B;
   const uint64_t words = mk_gb_work_words(nmembers, (uint32_t)nslices);
   const size_t scratch_bytes = mk_gb_scratch_bytes(nspans);
-  rc = mk_infl_grow(h, &h->d_comp, &h->comp_cap, stage_bytes + 64);
-  if (!rc) rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(text_end));
-  if (!rc) rc = mk_infl_grow(h, &h->d_status, &h->status_cap, words);
-  if (!rc) rc = mk_infl_grow_pinned(h, &h->h_status, &h->h_status_cap, 5u * (uint64_t)nmembers);
-  if (rc) return rc;
+  MK_INFL_HIP(h, mk_grow(&h->d_comp, &h->comp_cap, stage_bytes + 64, false));
+  MK_INFL_HIP(h, mk_grow(&h->d_text, &h->text_cap, mk_fq_buf_bytes(text_end), false));
+  MK_INFL_HIP(h, mk_grow(&h->d_status, &h->status_cap, words, false));
+  MK_INFL_HIP(h, mk_grow(&h->h_status, &h->h_status_cap, 5u * (uint64_t)nmembers, true));
   MK_INFL_HIP(h, mk_dev_alloc(&B.d_scratch, scratch_bytes));
   MK_INFL_HIP(h, mk_dev_alloc(&B.d_win, mk_gb_win_bytes(nspans)));
   MK_INFL_HIP(h, mk_dev_alloc(&B.d_syms, mk_gb_sym_bytes(nsyms)));

@@ -20,24 +20,8 @@
  *                        Safety: loads stay inside the member's payload rounded to 16 bytes, stores inside the ISIZE bytes at the
  *                        member's offset, every loop consumes input bits or produces output bytes and is bounded by the two sizes;
  *                        malformed data ends the member with a status (MK_INFL_*), written with an ordinary store.
- *   mk_fq_count_kernel   newlines per 4 KiB tile of the text and the last one's place
- *   mk_fq_scan_kernel    one workgroup: exclusive prefix over the tiles (= the line number at every tile's start), the number of
- *                        complete records, the first member with a bad status
- *   mk_fq_reduce_kernel  a wave per tile, a lane per 64 bytes: every newline's line number and the newline in front of it (from the
- *                        lanes' bit masks; from the text in front of the tile only for the tile's first) -> the longest line, the
- *                        longest sequence line of a complete record, the end of the last complete record
- *   mk_fq_rows_kernel    the same walk; the sequence lines found are copied by the whole wave, four bytes a lane, zero-padded
- *   mk_fq_carry_kernel   what lies behind the last complete record moves in front of the next chunk's text
- * The framing rule is mk_fastq_frame_range's (host/mk_frontend.c) and depends on line numbers only: record r is lines 4r..4r+3, it
- * gives a row iff its fourth line has at least one byte, the row is line 4r+1 with its '\n'.  (One difference, outside the contract
- * either way: a line of 4095+ characters is refused wherever it stands, also in a last record that lacks lines.)
- *   mk_fq_reduce_q_kernel / mk_fq_rows_q_kernel / mk_fq_first_q_kernel
- *                        the same for fastq2co's reader (dist without -A: -n, -Q), whose rule is mk_fastq_frame_q_range's: record r
- *                        gives a row iff all four of its lines end in '\n', the row is line 4r+1 with the bases whose byte of line
- *                        4r+3 is below -Q written as 'N'.  The reduce walk also leaves where every record's quality line starts and
- *                        how long it is (8 bytes a record); the rows kernel masks while it copies.  The first record of a file that
- *                        holds no complete one is walked all the same (iseq2comem.c:343-349): one wave does that serially.  No
- *                        windows: a line of 4095+ characters is refused, the caller takes the host framer for such a file.
+ * mk_fq_frame.hip.h (included behind the kernels): the FASTQ framing of text in HBM -- mk_fq_* kernels for both readers' rules and
+ *                        mk_fq_framer, the host-side sequence the BGZF route, the gunzip route and the test entry points all run.
  * mk_gunzip.hip.h (included last): ONE gzip member of any size by many waves -- block-start finder, decode to 16-bit symbols with
  *                        markers, window chain, resolve -- around this file's bit reader, table builder and CRC kernels.
  * mk_gunzip_batch.hip.h (behind it): a BATCH of gzip genome files, many waves per file, as one launch sequence without a host wait:
@@ -64,18 +48,8 @@
 #define MK_INFL_WIN 1024u      /* bytes of the compressed stream a wave holds in LDS */
 #define MK_INFL_LBITS 10u
 #define MK_INFL_DBITS 8u
-#define MK_FQ_TILE 4096u       /* text bytes per wave */
-#define MK_FQ_WAVES 4u
-#define MK_FQ_CARRY 16384u     /* room in front of a chunk's text: four lines of at most 4095 bytes (more means a line that long) */
-#define MK_FQ_LINE_MAX 4096u   /* MK_FQ_LEN: a line of this many bytes with its '\n' is refused (mk_frontend.c) */
 
 namespace {
-
-struct mk_fq_res {
-  uint32_t nl, nrec, consumed, maxline, maxseq; /* text coordinates */
-  uint32_t bad_block, bad_status;               /* first member with a status != 0 (0xffffffff: none) */
-  uint32_t pad;
-};
 
 __device__ __forceinline__ void mk_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -495,297 +469,6 @@ __global__ void __launch_bounds__(64) mk_crc32_combine_kernel(const mk_infl_blk 
   if (status[f] == MK_INFL_OK && crc != blks[f].crc) status[f] = MK_INFL_CRC;
 }
 
-/* ---- FASTQ framing of text in HBM ---------------------------------------------------------------------------------------------
- * `buf` is a 16-byte aligned buffer, the text is buf[t0, e1); tiles and positions are in buffer coordinates, the buffer is
- * allocated up to the end of the last tile (what lies outside [t0, e1) is loaded and masked, never used). */
-__device__ __forceinline__ uint32_t mk_nl4(uint32_t w) { /* bit k: byte k of w is '\n' */
-  const uint32_t x = w ^ 0x0a0a0a0au;
-  const uint32_t t = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
-  return ((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u);
-}
-__device__ __forceinline__ uint64_t mk_fq_mask(const uint8_t *buf, uint32_t b, uint32_t t0, uint32_t e1) {
-  if (b >= e1 || b + 64u <= t0) return 0ull;
-  uint64_t m = 0;
-  const uint4 *p = (const uint4 *)(buf + b);
-  for (uint32_t q = 0; q < 4u; q++) {
-    const uint4 v = p[q];
-    const uint64_t n16 = (uint64_t)(mk_nl4(v.x) | mk_nl4(v.y) << 4 | mk_nl4(v.z) << 8 | mk_nl4(v.w) << 12);
-    m |= n16 << (16u * q);
-  }
-  if (t0 > b) m &= ~0ull << (t0 - b);
-  if (e1 - b < 64u) m &= (1ull << (e1 - b)) - 1ull;
-  return m;
-}
-__device__ __forceinline__ uint32_t mk_wave_sum(uint32_t v) {
-  for (int o = 32; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
-__device__ __forceinline__ uint32_t mk_wave_max(uint32_t v) {
-  for (int o = 32; o; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)v, o); v = u > v ? u : v; }
-  return v;
-}
-
-__device__ __forceinline__ uint32_t mk_fq_stride_dev(uint32_t need) { return MK_ROW_PITCH(need); }
-
-__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_count_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
-                                                                       uint32_t *tile_cnt, uint32_t *tile_last) {
-  const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * MK_FQ_WAVES + (threadIdx.x >> 6);
-  if (tile >= ntiles) return;
-  const uint32_t b = tile * MK_FQ_TILE + 64u * lane;
-  const uint64_t m = mk_fq_mask(buf, b, t0, e1);
-  const uint32_t c = mk_wave_sum((uint32_t)__popcll(m));
-  const uint32_t last = mk_wave_max(m ? b + (63u - (uint32_t)__clzll(m)) + 1u : 0u); /* position + 1; 0: none */
-  if (lane == 0u) { tile_cnt[tile] = c; tile_last[tile] = last; }
-}
-
-/* one workgroup of 1024 threads: tile_cnt becomes its exclusive prefix; the totals of the chunk */
-__global__ void __launch_bounds__(1024) mk_fq_scan_kernel(uint32_t *tile_cnt, const uint32_t *tile_last, uint32_t ntiles, uint32_t t0, uint32_t e1,
-                                                          int final, const uint32_t *status, uint32_t nblocks, mk_fq_res *res) {
-  __shared__ uint32_t sums[1024];
-  __shared__ uint32_t s_last, s_bad;
-  const uint32_t t = threadIdx.x;
-  if (t == 0u) { s_last = 0u; s_bad = 0xffffffffu; }
-  __syncthreads();
-  const uint32_t per = (ntiles + 1023u) / 1024u;
-  const uint32_t lo = t * per < ntiles ? t * per : ntiles, hi = lo + per < ntiles ? lo + per : ntiles;
-  uint32_t s = 0, lastp = 0;
-  for (uint32_t i = lo; i < hi; i++) { s += tile_cnt[i]; const uint32_t l = tile_last[i]; lastp = l > lastp ? l : lastp; }
-  sums[t] = s;
-  if (lastp) atomicMax(&s_last, lastp);
-  for (uint32_t i = t; i < nblocks; i += 1024u) if (status[i]) atomicMin(&s_bad, i);
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024u; d <<= 1) { /* inclusive scan */
-    const uint32_t v = t >= d ? sums[t - d] : 0u;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  uint32_t run = sums[t] - s;
-  for (uint32_t i = lo; i < hi; i++) { const uint32_t c = tile_cnt[i]; tile_cnt[i] = run; run += c; }
-  if (t == 0u) {
-    const uint32_t n = e1 - t0, nl = sums[1023];
-    const uint32_t partial = s_last ? e1 - s_last : n; /* bytes behind the last newline */
-    const uint32_t lines = nl + (uint32_t)(final && partial > 0u);
-    mk_fq_res r;
-    r.nl = nl;
-    r.nrec = (final ? lines : nl) / 4u;
-    r.consumed = final ? n : 0u; /* (not final: the reduce kernel's thread that meets newline 4 * nrec - 1 says) */
-    r.maxline = final ? partial : 0u;
-    r.maxseq = 0u;
-    r.bad_block = s_bad;
-    r.bad_status = s_bad != 0xffffffffu ? status[s_bad] : 0u;
-    r.pad = 0u;
-    *res = r;
-  }
-}
-
-/* f(j, q, p) for every newline of the wave's tile, in the lane that holds it: p its position, j its number in the text (it ends
- * line j), q the position of the newline in front of it (t0 - 1 for j == 0).  A line of more than MK_FQ_LINE_MAX bytes may be
- * reported shorter, but never below MK_FQ_LINE_MAX + 1. */
-template <class F>
-__device__ __forceinline__ void mk_fq_walk(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t tile, uint32_t base, uint32_t lane, F f) {
-  const uint32_t b = tile * MK_FQ_TILE + 64u * lane;
-  uint64_t m = mk_fq_mask(buf, b, t0, e1);
-  const uint64_t have = __ballot(m != 0ull);
-  const uint32_t pc = (uint32_t)__popcll(m);
-  uint32_t ex = pc;
-  for (int o = 1; o < 64; o <<= 1) { const uint32_t u = (uint32_t)__shfl_up((int)ex, o); if ((int)lane >= o) ex += u; }
-  ex -= pc;
-  const uint64_t before = have & ((1ull << lane) - 1ull);
-  const int src = before ? 63 - __clzll(before) : 0;
-  const uint32_t mlo = (uint32_t)__shfl((int)(uint32_t)m, src), mhi = (uint32_t)__shfl((int)(uint32_t)(m >> 32), src);
-  if (!m) return;
-  uint32_t j = base + ex;
-  int32_t q;
-  if (before) q = (int32_t)(tile * MK_FQ_TILE + 64u * (uint32_t)src + (63u - (uint32_t)__clzll((uint64_t)mhi << 32 | mlo)));
-  else if (j == 0u) q = (int32_t)t0 - 1;
-  else { /* the tile's first newline: its predecessor lies in front of the tile, at most a line away */
-    const int32_t s = (int32_t)(tile * MK_FQ_TILE) - 1;
-    int32_t lim = s - (int32_t)MK_FQ_LINE_MAX;
-    if (lim < (int32_t)t0) lim = (int32_t)t0;
-    q = s;
-    while (q >= lim && buf[q] != (uint8_t)'\n') q--;
-  }
-  while (m) {
-    const uint32_t p = b + (uint32_t)__builtin_ctzll(m);
-    f(j, q, p);
-    q = (int32_t)p;
-    j++;
-    m &= m - 1ull;
-  }
-}
-
-__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_reduce_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
-                                                                        const uint32_t *tile_base, int final, mk_fq_res *res) {
-  const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * MK_FQ_WAVES + (threadIdx.x >> 6);
-  if (tile >= ntiles) return;
-  const uint32_t nrec = res->nrec;
-  uint32_t maxline = 0, maxseq = 0;
-  mk_fq_walk(buf, t0, e1, tile, tile_base[tile], lane, [&](uint32_t j, int32_t q, uint32_t p) {
-    const uint32_t len = (uint32_t)((int32_t)p - q);
-    maxline = len > maxline ? len : maxline;
-    if ((j & 3u) == 1u && (j >> 2) < nrec) maxseq = len > maxseq ? len : maxseq;
-    if (!final && nrec && j == 4u * nrec - 1u) res->consumed = p + 1u - t0;
-  });
-  maxline = mk_wave_max(maxline);
-  maxseq = mk_wave_max(maxseq);
-  if (lane == 0u) {
-    if (maxline) atomicMax(&res->maxline, maxline);
-    if (maxseq) atomicMax(&res->maxseq, maxseq);
-  }
-}
-
-/* rows [r0, r1) of the chunk: row r is line 4r + 1 with its '\n', zero-padded to `stride` */
-__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_rows_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
-                                                                      const uint32_t *tile_base, uint32_t r0, uint32_t r1, uint32_t stride,
-                                                                      uint8_t *rows) {
-  __shared__ uint32_t ev_start[MK_FQ_WAVES][MK_FQ_TILE / 4], ev_len[MK_FQ_WAVES][MK_FQ_TILE / 4], ev_row[MK_FQ_WAVES][MK_FQ_TILE / 4];
-  __shared__ uint32_t ev_n[MK_FQ_WAVES];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, tile = blockIdx.x * MK_FQ_WAVES + wave;
-  if (tile >= ntiles) return;
-  if (lane == 0u) ev_n[wave] = 0u;
-  mk_lds_fence();
-  /* sequence lines end at least four bytes apart: a tile holds at most MK_FQ_TILE / 4 of them */
-  mk_fq_walk(buf, t0, e1, tile, tile_base[tile], lane, [&](uint32_t j, int32_t q, uint32_t p) {
-    const uint32_t r = j >> 2;
-    if ((j & 3u) != 1u || r < r0 || r >= r1) return;
-    const uint32_t at = atomicAdd(&ev_n[wave], 1u);
-    ev_start[wave][at] = (uint32_t)(q + 1);
-    ev_len[wave][at] = (uint32_t)((int32_t)p - q);
-    ev_row[wave][at] = r - r0;
-  });
-  mk_lds_fence();
-  const uint32_t n = ev_n[wave];
-  for (uint32_t e = 0; e < n; e++) {
-    const uint32_t start = ev_start[wave][e], row = ev_row[wave][e];
-    uint32_t len = ev_len[wave][e];
-    if (len > stride) len = stride; /* (cannot happen: the stride comes from the longest of these lines) */
-    uint32_t *dst = (uint32_t *)(rows + (uint64_t)row * stride);
-    for (uint32_t o = 4u * lane; o < stride; o += 256u) {
-      uint32_t w = 0;
-      for (uint32_t k = 0; k < 4u; k++) if (o + k < len) w |= (uint32_t)buf[start + o + k] << (8u * k);
-      dst[o >> 2] = w;
-    }
-  }
-}
-
-/* ---- the same for fastq2co's reader (mk_fastq_frame_q_range, one row a record) -------------------------------------------------
- * The scan kernel is launched with final == 0, so res->nrec = newlines / 4: only a record whose four lines are all terminated is a
- * row, final call or not.  This walk adds what the rows kernel needs: qinfo[2r] = where record r's quality line starts (behind
- * newline 4r + 2), qinfo[2r + 1] = its length with its '\n' (newline 4r + 3 minus the one in front of it), for r < nrec; both
- * newlines exist for such a record, so both words are written, and start + length <= e1.  final: what lies behind the last newline
- * is a line too (the longest-line test sees it).  Stores: res, and qinfo below 2 * min(nrec, qcap). */
-__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_reduce_q_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
-                                                                          const uint32_t *tile_base, int final, mk_fq_res *res,
-                                                                          uint32_t *qinfo, uint32_t qcap) {
-  const uint32_t lane = threadIdx.x & 63u, tile = blockIdx.x * MK_FQ_WAVES + (threadIdx.x >> 6);
-  if (tile >= ntiles) return;
-  const uint32_t nl = res->nl;
-  uint32_t nrec = res->nrec;
-  if (nrec > qcap) nrec = qcap; /* (cannot happen: qcap >= text / 4 >= newlines / 4) */
-  uint32_t maxline = 0, maxseq = 0;
-  mk_fq_walk(buf, t0, e1, tile, tile_base[tile], lane, [&](uint32_t j, int32_t q, uint32_t p) {
-    const uint32_t len = (uint32_t)((int32_t)p - q), r = j >> 2, w = j & 3u;
-    maxline = len > maxline ? len : maxline;
-    if (final && j + 1u == nl) { const uint32_t tail = e1 - (p + 1u); maxline = tail > maxline ? tail : maxline; }
-    if (r >= nrec) return;
-    if (w == 1u) maxseq = len > maxseq ? len : maxseq;
-    else if (w == 2u) qinfo[2u * r] = p + 1u;
-    else if (w == 3u) {
-      qinfo[2u * r + 1u] = len;
-      if (r + 1u == nrec) res->consumed = p + 1u - t0;
-    }
-  });
-  maxline = mk_wave_max(maxline);
-  maxseq = mk_wave_max(maxseq);
-  if (lane == 0u) {
-    if (maxline) atomicMax(&res->maxline, maxline);
-    if (maxseq) atomicMax(&res->maxseq, maxseq);
-  }
-}
-
-/* base i of a row: the sequence byte, or 'N' when its quality byte (signed, 0 behind the quality line's end) is below qmin */
-__device__ __forceinline__ uint32_t mk_fq_qbyte(const uint8_t *buf, uint32_t start, uint32_t L, uint32_t qs, uint32_t qn, int32_t qmin, uint32_t i) {
-  uint32_t c = buf[start + i];
-  if (i < L && qmin > -128) {
-    const int32_t qv = i < qn ? (int32_t)(int8_t)buf[qs + i] : 0;
-    if (qv < qmin) c = (uint32_t)'N';
-  }
-  return c;
-}
-
-/* rows [r0, r1) of the chunk, r1 <= nrec: row r is line 4r + 1 with its '\n' (always there), quality-masked, zero-padded.  Loads:
- * the sequence line the walk found, and qinfo's [start, start + length) clamped to [t0, e1). */
-__global__ void __launch_bounds__(64 * MK_FQ_WAVES) mk_fq_rows_q_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, uint32_t ntiles,
-                                                                        const uint32_t *tile_base, uint32_t r0, uint32_t r1, uint32_t stride,
-                                                                        const uint32_t *qinfo, int32_t qmin, uint8_t *rows) {
-  __shared__ uint32_t ev_start[MK_FQ_WAVES][MK_FQ_TILE / 4], ev_len[MK_FQ_WAVES][MK_FQ_TILE / 4], ev_row[MK_FQ_WAVES][MK_FQ_TILE / 4];
-  __shared__ uint32_t ev_n[MK_FQ_WAVES];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, tile = blockIdx.x * MK_FQ_WAVES + wave;
-  if (tile >= ntiles) return;
-  if (lane == 0u) ev_n[wave] = 0u;
-  mk_lds_fence();
-  mk_fq_walk(buf, t0, e1, tile, tile_base[tile], lane, [&](uint32_t j, int32_t q, uint32_t p) {
-    const uint32_t r = j >> 2;
-    if ((j & 3u) != 1u || r < r0 || r >= r1) return;
-    const uint32_t at = atomicAdd(&ev_n[wave], 1u);
-    ev_start[wave][at] = (uint32_t)(q + 1);
-    ev_len[wave][at] = (uint32_t)((int32_t)p - q);
-    ev_row[wave][at] = r - r0;
-  });
-  mk_lds_fence();
-  const uint32_t n = ev_n[wave];
-  for (uint32_t e = 0; e < n; e++) {
-    const uint32_t start = ev_start[wave][e], row = ev_row[wave][e];
-    uint32_t len = ev_len[wave][e];
-    if (len > stride) len = stride; /* (cannot happen: the stride comes from the longest of these lines) */
-    uint32_t qs = qinfo[2u * (r0 + row)], qn = qinfo[2u * (r0 + row) + 1u];
-    if (qs < t0 || qs > e1) { qs = t0; qn = 0u; } /* (cannot happen: the reduce walk wrote both from newlines of the text) */
-    if (qn > e1 - qs) qn = e1 - qs;
-    const uint32_t L = len - 1u; /* len >= 1: the line's '\n' */
-    uint32_t *dst = (uint32_t *)(rows + (uint64_t)row * stride);
-    for (uint32_t o = 4u * lane; o < stride; o += 256u) {
-      uint32_t w = 0;
-      for (uint32_t k = 0; k < 4u; k++) if (o + k < len) w |= mk_fq_qbyte(buf, start, L, qs, qn, qmin, o + k) << (8u * k);
-      dst[o >> 2] = w;
-    }
-  }
-}
-
-/* The first record of a file without a complete one (fewer than four newlines, so fewer than four lines of at most 4095 bytes: the
- * caller has checked the longest line): one wave finds the first three newlines, 64 bytes a step.  The sequence is line 2 without
- * its '\n', the quality line is line 4 if the text has one, as far as it goes.  The row goes to rows[0, MK_ROW_PITCH(L + 1)), which
- * is at most 4096 bytes; res->maxseq = L + 1 and res->nrec = 1 tell the host; a text without a second line leaves both as they are. */
-__global__ void __launch_bounds__(64) mk_fq_first_q_kernel(const uint8_t *buf, uint32_t t0, uint32_t e1, int32_t qmin, mk_fq_res *res, uint8_t *rows) {
-  const uint32_t lane = threadIdx.x;
-  uint32_t nlp[3] = {e1, e1, e1}, found = 0;
-  for (uint32_t b = t0; b < e1 && found < 3u; b += 64u) {
-    uint64_t m = __ballot(b + lane < e1 && buf[b + lane] == (uint8_t)'\n');
-    while (m && found < 3u) { nlp[found++] = b + (uint32_t)__builtin_ctzll(m); m &= m - 1ull; }
-  }
-  if (nlp[0] + 1u >= e1) return; /* no second line: no record */
-  const uint32_t start = nlp[0] + 1u;
-  uint32_t L = nlp[1] - start;
-  if (L > MK_FQ_LINE_MAX - 1u) L = MK_FQ_LINE_MAX - 1u; /* (cannot happen, see above) */
-  const uint32_t qs = nlp[2] < e1 ? nlp[2] + 1u : e1, qn = e1 - qs;
-  const uint32_t stride = mk_fq_stride_dev(L + 1u);
-  uint32_t *dst = (uint32_t *)rows;
-  for (uint32_t o = 4u * lane; o < stride; o += 256u) {
-    uint32_t w = 0;
-    for (uint32_t k = 0; k < 4u; k++) {
-      if (o + k < L) w |= mk_fq_qbyte(buf, start, L, qs, qn, qmin, o + k) << (8u * k);
-      else if (o + k == L) w |= (uint32_t)'\n' << (8u * k);
-    }
-    dst[o >> 2] = w;
-  }
-  if (lane == 0u) { res->maxseq = L + 1u; res->nrec = 1u; }
-}
-
-/* src[from, from + n) -> dst[to, to + n): the bytes behind a chunk's last complete record, n <= MK_FQ_CARRY */
-__global__ void __launch_bounds__(256) mk_fq_carry_kernel(const uint8_t *src, uint32_t from, uint8_t *dst, uint32_t to, uint32_t n) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[to + i] = src[from + i];
-}
-
 double mk_now_s() {
   struct timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -794,17 +477,30 @@ double mk_now_s() {
 
 } /* namespace */
 
+/* *p holds `need` elements afterwards (device memory, or pinned host memory): grown with room to spare, what it held is lost */
+template <class T>
+static hipError_t mk_grow(T **p, uint64_t *cap, uint64_t need, bool pinned) {
+  if (need == 0) need = 1;
+  if (*p && need <= *cap) return hipSuccess;
+  if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); }
+  *p = nullptr; *cap = 0;
+  const uint64_t c = need + need / 8 + 256;
+  const hipError_t r = pinned ? mk_pin_alloc(p, c * sizeof(T), hipHostMallocDefault) : mk_dev_alloc(p, c * sizeof(T));
+  if (r == hipSuccess) *cap = c;
+  return r;
+}
+
+#include "mk_fq_frame.hip.h"
+
 struct mk_inflate {
   int device = 0;
   hipStream_t stream = nullptr;
   /* the test entry points' buffers (mk_sketch_push_bgzf keeps its own) */
-  uint8_t *h_stage = nullptr, *d_comp = nullptr, *d_text = nullptr, *d_rows = nullptr;
-  uint64_t stage_cap = 0, comp_cap = 0, text_cap = 0, rows_cap = 0;
-  uint32_t *d_status = nullptr, *h_status = nullptr, *d_tile_cnt = nullptr, *d_tile_last = nullptr;
-  uint64_t status_cap = 0, h_status_cap = 0, tiles_cap = 0, tiles_last_cap = 0;
-  uint32_t *d_qinfo = nullptr; /* mk_fastq_frame_q_device: start and length of every record's quality line */
-  uint64_t qinfo_cap = 0;
-  mk_fq_res *d_res = nullptr, *h_res = nullptr;
+  uint8_t *h_stage = nullptr, *d_comp = nullptr, *d_text = nullptr;
+  uint64_t stage_cap = 0, comp_cap = 0, text_cap = 0;
+  uint32_t *d_status = nullptr, *h_status = nullptr;
+  uint64_t status_cap = 0, h_status_cap = 0;
+  mk_fq_framer fq; /* mk_fastq_frame_device, mk_fastq_frame_q_device */
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   double inflate_ms = 0.0, frame_ms = 0.0;
   uint64_t stream_members = 0; /* of the last mk_inflate_stream */
@@ -827,29 +523,6 @@ static int mk_infl_fail(mk_inflate *h, int code, const char *fmt, ...) {
     if (_r != hipSuccess) return mk_infl_fail(h, MK_ERR_HIP, "%s: %s", #call, hipGetErrorString(_r)); \
   } while (0)
 
-template <class T>
-static int mk_infl_grow(mk_inflate *h, T **p, uint64_t *cap, uint64_t need) {
-  if (need == 0) need = 1;
-  if (need <= *cap && *p) return MK_OK;
-  (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  const uint64_t c = need + need / 8 + 256;
-  MK_INFL_HIP(h, mk_dev_alloc(p, c * sizeof(T)));
-  *cap = c;
-  return MK_OK;
-}
-template <class T>
-static int mk_infl_grow_pinned(mk_inflate *h, T **p, uint64_t *cap, uint64_t need) {
-  if (need == 0) need = 1;
-  if (need <= *cap && *p) return MK_OK;
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr; *cap = 0;
-  const uint64_t c = need + need / 8 + 256;
-  MK_INFL_HIP(h, mk_pin_alloc(p, c * sizeof(T), hipHostMallocDefault));
-  *cap = c;
-  return MK_OK;
-}
-
 extern "C" int mk_inflate_create(int device, mk_inflate **out) {
   if (!out) return MK_ERR_ARG;
   *out = nullptr;
@@ -865,8 +538,7 @@ extern "C" int mk_inflate_create(int device, mk_inflate **out) {
     return mk_infl_fail(nullptr, MK_ERR_NO_DEVICE, "hipSetDevice(%d) failed", device);
   }
   hipError_t r = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (r == hipSuccess) r = mk_dev_alloc(&h->d_res, sizeof(mk_fq_res));
-  if (r == hipSuccess) r = mk_pin_alloc(&h->h_res, sizeof(mk_fq_res), hipHostMallocDefault);
+  if (r == hipSuccess) r = h->fq.setup(false, 0);
   for (int i = 0; i < 4 && r == hipSuccess; i++) r = hipEventCreate(&h->ev[i]);
   if (r != hipSuccess) {
     mk_infl_fail(nullptr, MK_ERR_NOMEM, "inflate allocation: %s", hipGetErrorString(r));
@@ -881,9 +553,9 @@ extern "C" int mk_inflate_destroy(mk_inflate *h) {
   if (!h) return MK_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void *dev[] = {h->d_comp, h->d_text, h->d_rows, h->d_status, h->d_tile_cnt, h->d_tile_last, h->d_qinfo, h->d_res};
+  void *dev[] = {h->d_comp, h->d_text, h->d_status};
   for (void *p : dev) (void)hipFree(p);
-  void *pin[] = {h->h_stage, h->h_status, h->h_res};
+  void *pin[] = {h->h_stage, h->h_status};
   for (void *p : pin) if (p) (void)hipHostFree(p);
   for (hipEvent_t e : h->ev) if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -915,54 +587,6 @@ hipError_t mk_gz_launch(hipStream_t s, const uint8_t *d_comp, const void *d_tab,
   hipLaunchKernelGGL(mk_crc32_combine_kernel, dim3((n + 63u) / 64u), dim3(64), 0, s, blks, slice0s, n, (const uint32_t *)(d_work + 4u * (size_t)n), d_work, d_work + 3u * (size_t)n);
   return hipGetLastError();
 }
-static inline uint32_t mk_fq_ntiles(uint32_t e1) { return e1 ? (e1 + MK_FQ_TILE - 1) / MK_FQ_TILE : 1u; }
-/* bytes a text buffer needs for text that ends at buffer position e1: whole tiles */
-static inline uint64_t mk_fq_buf_bytes(uint64_t e1) { return ((e1 + MK_FQ_TILE - 1) / MK_FQ_TILE + 1) * (uint64_t)MK_FQ_TILE; }
-/* count + scan + reduce: *d_res is complete when the stream gets there */
-static hipError_t mk_launch_frame_count(hipStream_t s, const uint8_t *d_buf, uint32_t t0, uint32_t e1, int final, uint32_t *d_tile_cnt, uint32_t *d_tile_last,
-                                        const uint32_t *d_status, uint32_t nblocks, mk_fq_res *d_res) {
-  const uint32_t nt = mk_fq_ntiles(e1), grid = (nt + MK_FQ_WAVES - 1) / MK_FQ_WAVES;
-  hipLaunchKernelGGL(mk_fq_count_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, d_tile_cnt, d_tile_last);
-  hipLaunchKernelGGL(mk_fq_scan_kernel, dim3(1), dim3(1024), 0, s, d_tile_cnt, (const uint32_t *)d_tile_last, nt, t0, e1, final, d_status, nblocks, d_res);
-  hipLaunchKernelGGL(mk_fq_reduce_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, (const uint32_t *)d_tile_cnt, final, d_res);
-  return hipGetLastError();
-}
-static hipError_t mk_launch_frame_rows(hipStream_t s, const uint8_t *d_buf, uint32_t t0, uint32_t e1, const uint32_t *d_tile_cnt, uint32_t r0, uint32_t r1,
-                                       uint32_t stride, uint8_t *d_rows) {
-  if (r1 <= r0) return hipSuccess;
-  const uint32_t nt = mk_fq_ntiles(e1), grid = (nt + MK_FQ_WAVES - 1) / MK_FQ_WAVES;
-  hipLaunchKernelGGL(mk_fq_rows_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, d_tile_cnt, r0, r1, stride, d_rows);
-  return hipGetLastError();
-}
-static inline uint32_t mk_fq_stride(uint32_t maxseq) { const uint32_t need = maxseq ? maxseq : 1u; return MK_ROW_PITCH(need); }
-
-/* fastq2co's reader.  Records a text of n bytes can hold: four newlines each */
-static inline uint32_t mk_fq_qcap(uint64_t n) { return (uint32_t)(n / 4u + 1u); }
-static hipError_t mk_launch_frame_count_q(hipStream_t s, const uint8_t *d_buf, uint32_t t0, uint32_t e1, int final, uint32_t *d_tile_cnt, uint32_t *d_tile_last,
-                                          const uint32_t *d_status, uint32_t nblocks, mk_fq_res *d_res, uint32_t *d_qinfo, uint32_t qcap) {
-  const uint32_t nt = mk_fq_ntiles(e1), grid = (nt + MK_FQ_WAVES - 1) / MK_FQ_WAVES;
-  hipLaunchKernelGGL(mk_fq_count_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, d_tile_cnt, d_tile_last);
-  hipLaunchKernelGGL(mk_fq_scan_kernel, dim3(1), dim3(1024), 0, s, d_tile_cnt, (const uint32_t *)d_tile_last, nt, t0, e1, 0, d_status, nblocks, d_res);
-  hipLaunchKernelGGL(mk_fq_reduce_q_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, (const uint32_t *)d_tile_cnt, final, d_res, d_qinfo, qcap);
-  return hipGetLastError();
-}
-static hipError_t mk_launch_frame_rows_q(hipStream_t s, const uint8_t *d_buf, uint32_t t0, uint32_t e1, const uint32_t *d_tile_cnt, uint32_t r0, uint32_t r1,
-                                         uint32_t stride, const uint32_t *d_qinfo, int32_t qmin, uint8_t *d_rows) {
-  if (r1 <= r0) return hipSuccess;
-  const uint32_t nt = mk_fq_ntiles(e1), grid = (nt + MK_FQ_WAVES - 1) / MK_FQ_WAVES;
-  hipLaunchKernelGGL(mk_fq_rows_q_kernel, dim3(grid), dim3(64 * MK_FQ_WAVES), 0, s, d_buf, t0, e1, nt, d_tile_cnt, r0, r1, stride, d_qinfo, qmin, d_rows);
-  return hipGetLastError();
-}
-/* what the read-back of mk_launch_frame_count_q means on the host: on a final call everything is consumed and a text without a
- * newline is one line.  Returns whether mk_fq_first_q_kernel must look at the text: a final call, no record so far, none here, and
- * a first line that ends (whether a second one follows it is the kernel's to see). */
-static inline bool mk_fq_res_q(mk_fq_res &r, uint32_t n, int final, uint64_t records_before) {
-  if (!final) return false;
-  r.consumed = n;
-  if (r.nl == 0u && n > r.maxline) r.maxline = n;
-  return records_before == 0 && r.nrec == 0u && r.nl > 0u;
-}
-
 /* ---- the two entry points with a copy-back (tests, tools) ---------------------------------------------------------------------- */
 extern "C" int mk_inflate_blocks(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, const mk_bgzf_block *blocks, uint64_t nblocks,
                                  uint8_t *out_host, size_t out_cap, uint32_t *status) {
@@ -979,12 +603,11 @@ extern "C" int mk_inflate_blocks(mk_inflate *h, const uint8_t *comp, size_t comp
   if (out_host && out_cap < text_end) return mk_infl_fail(h, MK_ERR_ARG, "mk_inflate_blocks: out_cap too small");
   MK_INFL_HIP(h, hipSetDevice(h->device));
   const uint64_t tab_at = (comp_bytes + 15u) & ~(uint64_t)15u, stage_bytes = tab_at + nblocks * sizeof(mk_infl_blk);
-  int rc = mk_infl_grow_pinned(h, &h->h_stage, &h->stage_cap, stage_bytes);
-  if (!rc) rc = mk_infl_grow(h, &h->d_comp, &h->comp_cap, stage_bytes + 64);
-  if (!rc) rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(text_end));
-  if (!rc) rc = mk_infl_grow(h, &h->d_status, &h->status_cap, nblocks);
-  if (!rc) rc = mk_infl_grow_pinned(h, &h->h_status, &h->h_status_cap, nblocks);
-  if (rc) return rc;
+  MK_INFL_HIP(h, mk_grow(&h->h_stage, &h->stage_cap, stage_bytes, true));
+  MK_INFL_HIP(h, mk_grow(&h->d_comp, &h->comp_cap, stage_bytes + 64, false));
+  MK_INFL_HIP(h, mk_grow(&h->d_text, &h->text_cap, mk_fq_buf_bytes(text_end), false));
+  MK_INFL_HIP(h, mk_grow(&h->d_status, &h->status_cap, nblocks, false));
+  MK_INFL_HIP(h, mk_grow(&h->h_status, &h->h_status_cap, nblocks, true));
   memcpy(h->h_stage, comp, comp_bytes);
   mk_infl_blk *tab = (mk_infl_blk *)(h->h_stage + tab_at);
   for (uint64_t i = 0; i < nblocks; i++) {
@@ -1022,12 +645,11 @@ extern "C" int mk_inflate_members(mk_inflate *h, const uint8_t *comp, size_t com
   MK_INFL_HIP(h, hipSetDevice(h->device));
   const uint64_t tab_at = (comp_bytes + 15u) & ~(uint64_t)15u, stage_bytes = tab_at + mk_gz_table_bytes(nmembers);
   const uint64_t words = mk_gz_work_words(nmembers, (uint32_t)nslices);
-  int rc = mk_infl_grow_pinned(h, &h->h_stage, &h->stage_cap, stage_bytes);
-  if (!rc) rc = mk_infl_grow(h, &h->d_comp, &h->comp_cap, stage_bytes + 64);
-  if (!rc) rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(text_end));
-  if (!rc) rc = mk_infl_grow(h, &h->d_status, &h->status_cap, words);
-  if (!rc) rc = mk_infl_grow_pinned(h, &h->h_status, &h->h_status_cap, 4u * (uint64_t)nmembers);
-  if (rc) return rc;
+  MK_INFL_HIP(h, mk_grow(&h->h_stage, &h->stage_cap, stage_bytes, true));
+  MK_INFL_HIP(h, mk_grow(&h->d_comp, &h->comp_cap, stage_bytes + 64, false));
+  MK_INFL_HIP(h, mk_grow(&h->d_text, &h->text_cap, mk_fq_buf_bytes(text_end), false));
+  MK_INFL_HIP(h, mk_grow(&h->d_status, &h->status_cap, words, false));
+  MK_INFL_HIP(h, mk_grow(&h->h_status, &h->h_status_cap, 4u * (uint64_t)nmembers, true));
   memcpy(h->h_stage, comp, comp_bytes);
   memset(h->h_stage + comp_bytes, 0, tab_at - comp_bytes);
   mk_infl_blk *tab = (mk_infl_blk *)(h->h_stage + tab_at);
@@ -1055,101 +677,73 @@ extern "C" int mk_inflate_members(mk_inflate *h, const uint8_t *comp, size_t com
   return MK_OK;
 }
 
-extern "C" int mk_fastq_frame_device(mk_inflate *h, const uint8_t *text, size_t n, int final, uint8_t *rows_host, size_t rows_cap,
-                                     uint32_t *stride, uint64_t *nrows, size_t *consumed, uint32_t *longest) {
-  if (!h || (!text && n) || !stride || !nrows || !consumed) return MK_ERR_ARG;
-  if (n >= (1ull << 30)) return mk_infl_fail(h, MK_ERR_ARG, "mk_fastq_frame_device: at most 2^30 bytes a call");
+#define MK_FRAME_PORTION ((uint64_t)1 << 20) /* row bytes the test entries take back at a time: the routes' portion loop at small sizes */
+
+/* both entries: occ == false is mk_fastq_frame's rule, occ == true mk_fastq_frame_q's (qmin, records_before) */
+static int mk_frame_device(mk_inflate *h, const char *who, bool occ, const uint8_t *text, size_t n, int final, int32_t qmin, uint64_t records_before,
+                           uint8_t *rows_host, size_t rows_cap, uint32_t *stride, uint64_t *nrows, size_t *consumed, uint32_t *longest) {
+  if (n >= (1ull << 30)) return mk_infl_fail(h, MK_ERR_ARG, "%s: at most 2^30 bytes a call", who);
   MK_INFL_HIP(h, hipSetDevice(h->device));
-  const uint32_t t0 = 0, e1 = (uint32_t)n, nt = mk_fq_ntiles(e1);
-  int rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(e1));
-  if (!rc) rc = mk_infl_grow(h, &h->d_tile_cnt, &h->tiles_cap, nt);
-  if (!rc) rc = mk_infl_grow(h, &h->d_tile_last, &h->tiles_last_cap, nt);
-  if (rc) return rc;
+  mk_fq_framer &F = h->fq;
+  const uint32_t e1 = (uint32_t)n;
+  MK_INFL_HIP(h, F.setup(occ, qmin));
+  MK_INFL_HIP(h, mk_grow(&h->d_text, &h->text_cap, mk_fq_buf_bytes(e1), false));
+  MK_INFL_HIP(h, F.reserve(h->stream, e1, MK_FRAME_PORTION));
   if (n) MK_INFL_HIP(h, hipMemcpyAsync(h->d_text, text, n, hipMemcpyHostToDevice, h->stream));
   MK_INFL_HIP(h, hipEventRecord(h->ev[2], h->stream));
-  MK_INFL_HIP(h, mk_launch_frame_count(h->stream, h->d_text, t0, e1, final != 0, h->d_tile_cnt, h->d_tile_last, nullptr, 0, h->d_res));
-  MK_INFL_HIP(h, hipMemcpyAsync(h->h_res, h->d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, h->stream));
-  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
-  const mk_fq_res r = *h->h_res;
-  if (longest) *longest = r.maxline;
-  *nrows = 0; *consumed = 0; *stride = mk_fq_stride(r.maxseq);
-  if (r.maxline >= MK_FQ_LINE_MAX) return mk_infl_fail(h, MK_ERR_FORMAT, "a FASTQ line of 4095 characters or more");
-  const uint32_t sd = mk_fq_stride(r.maxseq);
-  if (rows_host && (uint64_t)r.nrec * sd > rows_cap) return mk_infl_fail(h, MK_ERR_ARG, "mk_fastq_frame_device: %u rows of %u bytes do not fit rows_cap", r.nrec, sd);
-  rc = mk_infl_grow(h, &h->d_rows, &h->rows_cap, (uint64_t)r.nrec * sd);
-  if (rc) return rc;
-  MK_INFL_HIP(h, mk_launch_frame_rows(h->stream, h->d_text, t0, e1, h->d_tile_cnt, 0, r.nrec, sd, h->d_rows));
+  MK_INFL_HIP(h, F.count(h->stream, h->d_text, 0, e1, final != 0, nullptr, 0));
+  mk_fq_chunk c;
+  MK_INFL_HIP(h, F.result(records_before, &c));
+  if (longest) *longest = c.r.maxline;
+  *nrows = 0; *consumed = 0; *stride = c.stride;
+  if (c.long_line) return mk_infl_fail(h, MK_ERR_FORMAT, "a FASTQ line of 4095 characters or more");
+  uint64_t at = 0; /* row bytes copied back so far */
+  auto push = [&](const uint8_t *d_rows, uint32_t sd, uint32_t k) -> int {
+    if (!rows_host) return MK_OK;
+    const uint32_t all = c.first ? k : c.r.nrec; /* (the first record's row is the only one) */
+    if ((uint64_t)all * sd > rows_cap) return mk_infl_fail(h, MK_ERR_ARG, "%s: %u rows of %u bytes do not fit rows_cap", who, all, sd);
+    MK_INFL_HIP(h, hipMemcpyAsync(rows_host + at, d_rows, (uint64_t)k * sd, hipMemcpyDeviceToHost, h->stream));
+    at += (uint64_t)k * sd;
+    return MK_OK;
+  };
+  mk_fq_handed out;
+  MK_INFL_HIP(h, F.rows(h->stream, c, push, &out));
+  *stride = out.stride;
+  if (out.push_rc) { (void)hipStreamSynchronize(h->stream); return out.push_rc; }
   MK_INFL_HIP(h, hipEventRecord(h->ev[3], h->stream));
-  if (rows_host && r.nrec) MK_INFL_HIP(h, hipMemcpyAsync(rows_host, h->d_rows, (uint64_t)r.nrec * sd, hipMemcpyDeviceToHost, h->stream));
   MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
   float ms = 0.f;
   MK_INFL_HIP(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
   h->frame_ms = ms;
-  *nrows = r.nrec;
-  *consumed = r.consumed;
+  *nrows = out.rows;
+  *consumed = c.r.consumed;
   return MK_OK;
+}
+
+extern "C" int mk_fastq_frame_device(mk_inflate *h, const uint8_t *text, size_t n, int final, uint8_t *rows_host, size_t rows_cap,
+                                     uint32_t *stride, uint64_t *nrows, size_t *consumed, uint32_t *longest) {
+  if (!h || (!text && n) || !stride || !nrows || !consumed) return MK_ERR_ARG;
+  return mk_frame_device(h, "mk_fastq_frame_device", false, text, n, final, 0, 0, rows_host, rows_cap, stride, nrows, consumed, longest);
 }
 
 extern "C" int mk_fastq_frame_q_device(mk_inflate *h, const uint8_t *text, size_t n, int final, int32_t qmin, uint64_t records_before,
                                        uint8_t *rows_host, size_t rows_cap, uint32_t *stride, uint64_t *nrows, uint64_t *nrecords,
                                        size_t *consumed, uint32_t *longest) {
   if (!h || (!text && n) || !stride || !nrows || !nrecords || !consumed) return MK_ERR_ARG;
-  if (n >= (1ull << 30)) return mk_infl_fail(h, MK_ERR_ARG, "mk_fastq_frame_q_device: at most 2^30 bytes a call");
-  MK_INFL_HIP(h, hipSetDevice(h->device));
-  const uint32_t t0 = 0, e1 = (uint32_t)n, nt = mk_fq_ntiles(e1), qcap = mk_fq_qcap(n);
-  int rc = mk_infl_grow(h, &h->d_text, &h->text_cap, mk_fq_buf_bytes(e1));
-  if (!rc) rc = mk_infl_grow(h, &h->d_tile_cnt, &h->tiles_cap, nt);
-  if (!rc) rc = mk_infl_grow(h, &h->d_tile_last, &h->tiles_last_cap, nt);
-  if (!rc) rc = mk_infl_grow(h, &h->d_qinfo, &h->qinfo_cap, 2u * (uint64_t)qcap);
-  if (!rc) rc = mk_infl_grow(h, &h->d_rows, &h->rows_cap, MK_FQ_LINE_MAX); /* (the first record's row, whatever its stride) */
-  if (rc) return rc;
-  if (n) MK_INFL_HIP(h, hipMemcpyAsync(h->d_text, text, n, hipMemcpyHostToDevice, h->stream));
-  MK_INFL_HIP(h, hipEventRecord(h->ev[2], h->stream));
-  MK_INFL_HIP(h, mk_launch_frame_count_q(h->stream, h->d_text, t0, e1, final != 0, h->d_tile_cnt, h->d_tile_last, nullptr, 0, h->d_res, h->d_qinfo, qcap));
-  MK_INFL_HIP(h, hipMemcpyAsync(h->h_res, h->d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, h->stream));
-  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
-  mk_fq_res r = *h->h_res;
-  const bool first = mk_fq_res_q(r, e1, final != 0, records_before);
-  if (longest) *longest = r.maxline;
-  *nrows = 0; *nrecords = 0; *consumed = 0; *stride = mk_fq_stride(r.maxseq);
-  if (r.maxline >= MK_FQ_LINE_MAX) return mk_infl_fail(h, MK_ERR_FORMAT, "a FASTQ line of 4095 characters or more");
-  if (first) {
-    hipLaunchKernelGGL(mk_fq_first_q_kernel, dim3(1), dim3(64), 0, h->stream, (const uint8_t *)h->d_text, t0, e1, qmin, h->d_res, h->d_rows);
-    MK_INFL_HIP(h, hipGetLastError());
-    MK_INFL_HIP(h, hipMemcpyAsync(h->h_res, h->d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, h->stream));
-    MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
-    r.nrec = h->h_res->nrec;
-    r.maxseq = h->h_res->maxseq;
-  }
-  const uint32_t sd = mk_fq_stride(r.maxseq);
-  *stride = sd;
-  if (rows_host && (uint64_t)r.nrec * sd > rows_cap) return mk_infl_fail(h, MK_ERR_ARG, "mk_fastq_frame_q_device: %u rows of %u bytes do not fit rows_cap", r.nrec, sd);
-  if (!first) {
-    rc = mk_infl_grow(h, &h->d_rows, &h->rows_cap, (uint64_t)r.nrec * sd);
-    if (rc) return rc;
-    MK_INFL_HIP(h, mk_launch_frame_rows_q(h->stream, h->d_text, t0, e1, h->d_tile_cnt, 0, r.nrec, sd, h->d_qinfo, qmin, h->d_rows));
-  }
-  MK_INFL_HIP(h, hipEventRecord(h->ev[3], h->stream));
-  if (rows_host && r.nrec) MK_INFL_HIP(h, hipMemcpyAsync(rows_host, h->d_rows, (uint64_t)r.nrec * sd, hipMemcpyDeviceToHost, h->stream));
-  MK_INFL_HIP(h, hipStreamSynchronize(h->stream));
-  float ms = 0.f;
-  MK_INFL_HIP(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-  h->frame_ms = ms;
-  *nrows = r.nrec;
-  *nrecords = r.nrec;
-  *consumed = r.consumed;
-  return MK_OK;
+  *nrecords = 0;
+  const int rc = mk_frame_device(h, "mk_fastq_frame_q_device", true, text, n, final, qmin, records_before, rows_host, rows_cap, stride, nrows, consumed, longest);
+  if (rc == MK_OK) *nrecords = *nrows;
+  return rc;
 }
 
 /* ---- the route bound to an engine -------------------------------------------------------------------------------------------- */
 namespace {
-struct mk_bgzf_run { /* everything mk_sketch_push_bgzf allocates, released on every way out */
+struct mk_bgzf_run { /* everything mk_sketch_push_bgzf allocates beside its framer, released on every way out */
   mk_bgzf_block *blocks = nullptr;
   hipStream_t copy = nullptr;
-  uint8_t *h_stage[2] = {nullptr, nullptr}, *d_comp[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr}, *d_rows = nullptr;
-  uint32_t *d_status[2] = {nullptr, nullptr}, *d_tile_cnt = nullptr, *d_tile_last = nullptr, *d_qinfo = nullptr;
-  mk_fq_res *d_res = nullptr, *h_res = nullptr;
-  hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_res = nullptr, ev_i[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, ev_f[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint8_t *h_stage[2] = {nullptr, nullptr}, *d_comp[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr};
+  uint32_t *d_status[2] = {nullptr, nullptr};
+  hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_i[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
   ~mk_bgzf_run() {
     mk_bgzf_free(blocks);
     for (int s = 0; s < 2; s++) {
@@ -1158,10 +752,6 @@ struct mk_bgzf_run { /* everything mk_sketch_push_bgzf allocates, released on ev
       if (ev_up[s]) (void)hipEventDestroy(ev_up[s]);
       for (int k = 0; k < 2; k++) if (ev_i[s][k]) (void)hipEventDestroy(ev_i[s][k]);
     }
-    (void)hipFree(d_rows); (void)hipFree(d_tile_cnt); (void)hipFree(d_tile_last); (void)hipFree(d_qinfo); (void)hipFree(d_res);
-    if (h_res) (void)hipHostFree(h_res);
-    if (ev_res) (void)hipEventDestroy(ev_res);
-    for (hipEvent_t e : ev_f) if (e) (void)hipEventDestroy(e);
     if (copy) (void)hipStreamDestroy(copy);
   }
 };
@@ -1214,8 +804,7 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
   }
   const uint64_t stage_bytes = ((max_in + 15u) & ~(uint64_t)15u) + max_blocks * sizeof(mk_infl_blk);
   const uint64_t text_bytes = mk_fq_buf_bytes(MK_FQ_CARRY + max_text);
-  const uint32_t max_tiles = mk_fq_ntiles((uint32_t)(MK_FQ_CARRY + max_text));
-  const uint64_t rows_cap = (max_text + MK_FQ_CARRY > ((uint64_t)8 << 20) ? max_text + MK_FQ_CARRY : (uint64_t)8 << 20) + 4096u;
+  const uint64_t rows_bytes = (max_text + MK_FQ_CARRY > ((uint64_t)8 << 20) ? max_text + MK_FQ_CARRY : (uint64_t)8 << 20) + 4096u;
   MK_BGZF_HIP(hipSetDevice(device));
   MK_BGZF_HIP(hipStreamCreateWithFlags(&R.copy, hipStreamNonBlocking));
   for (int s = 0; s < 2; s++) {
@@ -1227,15 +816,9 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
     MK_BGZF_HIP(hipEventCreateWithFlags(&R.ev_up[s], hipEventDisableTiming));
     for (int k = 0; k < 2; k++) MK_BGZF_HIP(hipEventCreate(&R.ev_i[s][k]));
   }
-  MK_BGZF_HIP(mk_dev_alloc(&R.d_rows, rows_cap));
-  MK_BGZF_HIP(mk_dev_alloc(&R.d_tile_cnt, (uint64_t)max_tiles * sizeof(uint32_t)));
-  MK_BGZF_HIP(mk_dev_alloc(&R.d_tile_last, (uint64_t)max_tiles * sizeof(uint32_t)));
-  const uint32_t qcap = mk_fq_qcap(MK_FQ_CARRY + max_text);
-  if (occ) MK_BGZF_HIP(mk_dev_alloc(&R.d_qinfo, 2u * (uint64_t)qcap * sizeof(uint32_t)));
-  MK_BGZF_HIP(mk_dev_alloc(&R.d_res, sizeof(mk_fq_res)));
-  MK_BGZF_HIP(mk_pin_alloc(&R.h_res, sizeof(mk_fq_res), hipHostMallocDefault));
-  MK_BGZF_HIP(hipEventCreateWithFlags(&R.ev_res, hipEventDisableTiming));
-  for (int k = 0; k < 4; k++) MK_BGZF_HIP(hipEventCreate(&R.ev_f[k]));
+  mk_fq_framer F;
+  MK_BGZF_HIP(F.setup(occ, qmin));
+  MK_BGZF_HIP(F.reserve(S, MK_FQ_CARRY + max_text, rows_bytes));
 
   /* chunk k: file -> pinned staging -> device (copy stream), inflate behind it on the engine's stream */
   auto queue_inflate = [&](size_t k) -> int {
@@ -1267,78 +850,52 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
   rc = queue_inflate(0);
   if (rc) return rc;
   uint32_t carry = 0;
-  uint64_t ordinal = first_ordinal;
-  bool rows_timed = false;
+  mk_fq_handed out{};
+  auto push = [&](const uint8_t *d_rows, uint32_t stride, uint32_t nrows) -> int {
+    return mk_sketch_push_reads_device(e, d_rows, stride, nrows, first_ordinal + stats.rows + out.rows);
+  };
+  float ms = 0.f, rows_ms = 0.f;
   int result = MK_OK;
   for (size_t k = 0; k < chunks.size(); k++) {
     const mk_bgzf_chunk &c = chunks[k];
     const int s = (int)(k & 1u), final = k + 1 == chunks.size();
-    const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + (uint32_t)c.text, n = e1 - t0;
-    MK_BGZF_HIP(hipEventRecord(R.ev_f[0], S));
-    if (occ) MK_BGZF_HIP(mk_launch_frame_count_q(S, R.d_text[s], t0, e1, final, R.d_tile_cnt, R.d_tile_last, R.d_status[s], (uint32_t)(c.b1 - c.b0), R.d_res, R.d_qinfo, qcap));
-    else MK_BGZF_HIP(mk_launch_frame_count(S, R.d_text[s], t0, e1, final, R.d_tile_cnt, R.d_tile_last, R.d_status[s], (uint32_t)(c.b1 - c.b0), R.d_res));
-    MK_BGZF_HIP(hipEventRecord(R.ev_f[1], S));
-    MK_BGZF_HIP(hipMemcpyAsync(R.h_res, R.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
-    MK_BGZF_HIP(hipEventRecord(R.ev_res, S));
+    const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + (uint32_t)c.text;
+    MK_BGZF_HIP(F.count(S, R.d_text[s], t0, e1, final, R.d_status[s], (uint32_t)(c.b1 - c.b0)));
     if (!final) { /* the next chunk's bytes travel and inflate beside this one's framing and scan (its slots were chunk k - 1's, whose read-back has been waited for) */
       rc = queue_inflate(k + 1);
       if (rc) return rc;
     }
-    MK_BGZF_HIP(hipEventSynchronize(R.ev_res)); /* the one wait per chunk: rows, longest line, consumed, status */
-    mk_fq_res r = *R.h_res;
-    const bool first = occ && mk_fq_res_q(r, n, final, stats.rows);
-    float ms = 0.f;
+    mk_fq_chunk q;
+    MK_BGZF_HIP(F.result(stats.rows, &q)); /* the one wait per chunk: rows, longest line, consumed, status */
     MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_i[s][0], R.ev_i[s][1]));
     stats.inflate_ms += ms;
-    MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_f[0], R.ev_f[1]));
-    stats.frame_ms += ms;
-    if (rows_timed) { MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_f[2], R.ev_f[3])); stats.frame_ms += ms; rows_timed = false; }
-    if (r.bad_block != 0xffffffffu) {
-      stats.bad_block = (int64_t)(c.b0 + r.bad_block);
-      stats.bad_status = (int32_t)r.bad_status;
+    MK_BGZF_HIP(F.times(&ms, &rows_ms)); /* (the rows: the chunk before) */
+    stats.frame_ms += ms + rows_ms;
+    if (q.r.bad_block != 0xffffffffu) {
+      stats.bad_block = (int64_t)(c.b0 + q.r.bad_block);
+      stats.bad_status = (int32_t)q.r.bad_status;
       snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "BGZF block %llu: %s", (unsigned long long)stats.bad_block, mk_inflate_status_text(stats.bad_status));
       result = MK_ERR_FORMAT;
       break;
     }
-    if (r.maxline >= MK_FQ_LINE_MAX || (!final && n - r.consumed > MK_FQ_CARRY)) {
+    if (q.long_line) {
       snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "a FASTQ line of 4095 characters or more");
       result = MK_ERR_FORMAT;
       break;
     }
-    if (first) { /* no complete record in the whole file: its first one is walked all the same, if it has a sequence line */
-      hipLaunchKernelGGL(mk_fq_first_q_kernel, dim3(1), dim3(64), 0, S, (const uint8_t *)R.d_text[s], t0, e1, qmin, R.d_res, R.d_rows);
-      MK_BGZF_HIP(hipGetLastError());
-      MK_BGZF_HIP(hipMemcpyAsync(R.h_res, R.d_res, sizeof(mk_fq_res), hipMemcpyDeviceToHost, S));
-      MK_BGZF_HIP(hipStreamSynchronize(S));
-      if (R.h_res->nrec) {
-        rc = mk_sketch_push_reads_device(e, R.d_rows, mk_fq_stride(R.h_res->maxseq), 1, ordinal);
-        if (rc) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
-        ordinal++;
-        stats.rows++;
-      }
-    }
-    const uint32_t stride = mk_fq_stride(r.maxseq);
-    const uint32_t per = (uint32_t)(rows_cap / stride);
-    if (r.nrec) { MK_BGZF_HIP(hipEventRecord(R.ev_f[2], S)); }
-    for (uint32_t r0 = 0; r0 < r.nrec; r0 += per) {
-      const uint32_t r1 = r.nrec - r0 < per ? r.nrec : r0 + per;
-      if (occ) MK_BGZF_HIP(mk_launch_frame_rows_q(S, R.d_text[s], t0, e1, R.d_tile_cnt, r0, r1, stride, R.d_qinfo, qmin, R.d_rows));
-      else MK_BGZF_HIP(mk_launch_frame_rows(S, R.d_text[s], t0, e1, R.d_tile_cnt, r0, r1, stride, R.d_rows));
-      if (r0 == 0) { MK_BGZF_HIP(hipEventRecord(R.ev_f[3], S)); rows_timed = true; }
-      rc = mk_sketch_push_reads_device(e, R.d_rows, stride, r1 - r0, ordinal);
-      if (rc) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
-      ordinal += r1 - r0;
-    }
-    stats.rows += r.nrec;
-    carry = n - r.consumed;
+    MK_BGZF_HIP(F.rows(S, q, push, &out));
+    if (out.push_rc) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return out.push_rc; }
+    stats.rows += out.rows;
+    carry = out.carry;
     if (!final && carry) {
-      hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)R.d_text[s], t0 + r.consumed, R.d_text[s ^ 1], MK_FQ_CARRY - carry, carry);
+      hipLaunchKernelGGL(mk_fq_carry_kernel, dim3((carry + 255u) / 256u), dim3(256), 0, S, (const uint8_t *)R.d_text[s], t0 + q.r.consumed, R.d_text[s ^ 1], MK_FQ_CARRY - carry, carry);
       MK_BGZF_HIP(hipGetLastError());
     }
   }
   MK_BGZF_HIP(hipStreamSynchronize(S));
   MK_BGZF_HIP(hipStreamSynchronize(R.copy));
-  if (rows_timed) { float ms = 0.f; MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_f[2], R.ev_f[3])); stats.frame_ms += ms; }
+  MK_BGZF_HIP(F.times(&ms, &rows_ms));
+  stats.frame_ms += rows_ms;
   stats.blocks = nblocks; stats.chunks = chunks.size(); stats.comp_bytes = size; stats.text_bytes = total;
   stats.t_total_s = mk_now_s() - t_begin;
   if (st) *st = stats;

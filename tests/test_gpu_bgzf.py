@@ -292,6 +292,44 @@ def test_framer_long_lines(infl):
         assert infl.frame(bad, final=True)[5] == capi.MK_ERR_FORMAT
 
 
+PORTION = 1 << 20  # MK_FRAME_PORTION (mk_inflate.hip): row bytes the two entries take back at a time
+PITCH = 160        # MK_ROW_PITCH(151): the first record below has 150 bases, none has more
+
+
+def portion_text(nrec):
+    """nrec records of 100 to 150 bases, the first of 150; qualities on both sides of -Q 54"""
+    rs = np.random.RandomState(nrec)
+    lens = rs.randint(100, 151, nrec)
+    lens[0] = 150
+    bases = np.frombuffer(b"ACGTN", dtype=np.uint8)[rs.randint(0, 5, int(lens.sum()))].tobytes()
+    quals = rs.randint(33, 75, int(lens.sum()), dtype=np.uint8).tobytes()
+    out, at = [], 0
+    for i, n in enumerate(lens):
+        out.append(b"@r%d\n%s\n+\n%s\n" % (i, bases[at:at + n], quals[at:at + n]))
+        at += n
+    return b"".join(out)
+
+
+@pytest.mark.parametrize("nrec", [20000, PORTION // PITCH, PORTION // PITCH + 1])
+def test_framer_rows_in_more_than_one_portion(infl, nrec):
+    """the portion loop of mk_fq_framer::rows at sizes where it takes three trips (the last one partial), exactly one (a second
+    portion would be empty), and two (one row in the second), for both readers' rules, against the host framers"""
+    text = portion_text(nrec)
+    if nrec == 20000:
+        assert nrec * PITCH > 2 * PORTION  # cannot pass by fitting in one portion
+    else:
+        assert (nrec * PITCH <= PORTION) == (nrec == PORTION // PITCH) and (nrec + 1) * PITCH > PORTION
+    rows, stride, n, consumed, longest, rc = infl.frame(text, final=True)
+    assert rc == 0 and (stride, n, consumed) == (PITCH, nrec, len(text))
+    hrows, hn, hused, hrc = capi.fastq_frame(text, stride, final=True)
+    assert hrc == 0 and (hn, hused) == (n, consumed) and np.array_equal(hrows, rows)
+    rows, stride, n, nrecords, consumed, longest, rc = infl.frame_q(text, qmin=54, final=True)
+    assert rc == 0 and (stride, n, nrecords, consumed) == (PITCH, nrec, nrec, len(text))
+    hrows, hn, hrec, hused, hrc = capi.fastq_frame_q(text, stride, 22, qmin=54, final=True)
+    assert hrc == 0 and (hn, hrec, hused) == (n, nrecords, consumed) and np.array_equal(hrows, rows)
+    assert (rows == ord("N")).sum() > (np.frombuffer(text, dtype=np.uint8) == ord("N")).sum()  # the mask was at work
+
+
 # ---- the command line ---------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def shuf_files(tmp_path_factory):
