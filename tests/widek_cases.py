@@ -104,6 +104,15 @@ def planted_unituples(rs, P, n):
     return got[:n]
 
 
+def keys_of(P, uni, pf=None):
+    """the keys of accepted canonical k-mers (uint64 unituples): the outer halves joined, shifted by the dimension reduction, plus
+    the .shuf value pf of the inner substring (looked up when not given)"""
+    if pf is None:
+        pf = P.table[((uni & np.uint64(P.domask)) >> np.uint64(2 * P.out)).astype(np.int64)]
+    low = uni & np.uint64((1 << (2 * P.out)) - 1)
+    return (((uni & np.uint64(P.undomask)) + (low << np.uint64(2 * P.TL - 4 * P.out))) >> np.uint64(4 * P.drlevel)) + pf.astype(np.uint64)
+
+
 def colliding_partners(rs, P, uni):
     """for canonical accepted k-mers of a clamped geometry, DIFFERENT canonical accepted k-mers with the same key: another inner
     substring, whose pf differs by a multiple of 2^v (v = 4(subk - drlevel), the bits the shift vacated), and the outer context
@@ -212,8 +221,7 @@ class Input:
         pf = P.table[((uni & np.uint64(P.domask)) >> np.uint64(2 * P.out)).astype(np.int64)]
         acc = (pf >= P.dim_start) & (pf < P.dim_end)
         uni, pf, fwd, rc = uni[acc], pf[acc], fwd[acc], rc[acc]
-        low = uni & np.uint64((1 << (2 * P.out)) - 1)
-        key = (((uni & np.uint64(P.undomask)) + (low << np.uint64(2 * P.TL - 4 * P.out))) >> np.uint64(4 * P.drlevel)) + pf.astype(np.uint64)
+        key = keys_of(P, uni, pf)
         du, dk = np.unique(uni), np.unique(key)
         return {"keys": dk, "top_bit": int(np.count_nonzero(du >> np.uint64(4 * P.k - 1))), "fwd_canonical": int(np.count_nonzero(fwd < rc)),
                 "rc_canonical": int(np.count_nonzero(rc < fwd)), "collisions": int(du.size - dk.size)}
