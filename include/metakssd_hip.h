@@ -276,6 +276,17 @@ int mk_sketch_push_stream(mk_engine *e, const uint8_t *text, uint64_t n, int fin
  * mk_sketch_push_stream; text may be cut anywhere (the record left open by a piece waits in front of the next).  MK_MODE_KOC
  * sketches only (MK_ERR_STATE otherwise); not to be mixed with mk_sketch_push_stream in one sketch (MK_ERR_STATE). */
 int mk_sketch_push_fastq_long(mk_engine *e, const uint8_t *text, uint64_t n, int final);
+/* mk_sketch_push_fastq_long for text that lies in the memory of the engine's device, at any alignment (DESIGN.md 4.19's rule, 4.20):
+ * the same contract -- MK_MODE_KOC only, not after `final`, not mixed with mk_sketch_push_stream, below 2^31 bytes a call, a record
+ * of 2^31 bytes refused; MK_ERR_ARG for a pointer that is not this device's.  The text is copied behind the open record into the
+ * engine's own buffer on the engine's stream (mk_engine_get_stream): d_text is free once work queued later on that stream may
+ * overwrite it.  Returns with its work queued, as a pinned host push does; the next call on the engine waits.  The open record stays
+ * in HBM between pushes for both entries, so host and device pushes may alternate within one sketch.  After a failed push, or to
+ * abandon a sketch whose last push was not final: mk_sketch_finish (result dropped), then mk_sketch_begin. */
+int mk_sketch_push_fastq_long_device(mk_engine *e, const uint8_t *d_text, uint64_t n, int final);
+/* device milliseconds of the framing kernels (mk_fql_*, the carry kernel included) of all mk_sketch_push_fastq_long[_device] calls
+ * since mk_sketch_begin; waits for the last of them.  To be asked before the next mk_sketch_begin. */
+int mk_sketch_fastq_long_frame_ms(mk_engine *e, double *ms);
 int mk_sketch_finish(mk_engine *e, mk_result *out);
 /* mk_sketch_finish in two halves, for callers that sketch one input after another: _begin runs compaction, layout and dump (into
  * staging arrays in HBM), waits once for the counters and queues the copy of the result to the host on a stream of its own;
@@ -849,7 +860,14 @@ int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
  * (MK_ERR_FORMAT, st->bad_block == -1) may be reported after rows of earlier chunks have been pushed: such a file is inside
  * fastq2co's contract, so the caller abandons the sketch and reads the file through the host framer (mk_fastq_frame_q). */
 int mk_sketch_push_bgzf_q(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int32_t qmin, uint64_t first_ordinal, mk_bgzf_stats *st);
-const char *mk_bgzf_last_error(void); /* text of the calling thread's last failed mk_sketch_push_bgzf / mk_sketch_push_bgzf_q */
+/* The same file into a MK_MODE_KOC sketch by DESIGN.md 4.19's rule (reads of any length; 4.20): upload, inflate and CRC as above,
+ * but every chunk's text goes to mk_sketch_push_fastq_long_device -- no row framing, no MK_FQ_CARRY, no long-line status.  `final`
+ * goes with the last chunk (also an empty one); with final == 0 the record left open at the file's end waits for the next call's
+ * text, as in `zcat a b`.  st->rows stays 0, st->frame_ms is the time of the mk_fql_* and carry kernels.  A damaged member:
+ * MK_ERR_FORMAT with st->bad_block / st->bad_status, that chunk's text is not pushed; the sketch must be abandoned (mk_sketch_finish,
+ * result dropped, then mk_sketch_begin). */
+int mk_sketch_push_bgzf_long(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int final, mk_bgzf_stats *st);
+const char *mk_bgzf_last_error(void); /* text of the calling thread's last failed mk_sketch_push_bgzf / _q / _long, mk_sketch_push_gzip* */
 /* the stream the engine's kernels are queued on now and its device, for work that must be ordered with them (staged rows are
  * flushed first).  MK_ERR_STATE with MK_OPT_SPLIT_CUS (two queues: no single stream orders with the scan). */
 int mk_engine_get_stream(mk_engine *e, void **hip_stream, int *device);
@@ -997,6 +1015,13 @@ int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts 
  * bytes behind a slice's last complete record; the caller begins the sketch anew.  The framing keeps 8 bytes per record a slice of
  * 128 MiB can hold: 256 MiB for a full slice. */
 int mk_sketch_push_gzip_q(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int32_t qmin, uint64_t first_ordinal, mk_gunzip_stats *st);
+/* The text of mk_sketch_push_gzip (geometry, statuses, trailer check, MK_GUNZIP_MEMBERS unchanged) into a MK_MODE_KOC sketch by
+ * DESIGN.md 4.19's rule (reads of any length; 4.20): every batch's text goes to mk_sketch_push_fastq_long_device -- no row framing, no
+ * MK_FQ_CARRY, no long-line status, no slices.  `final` goes with the last batch (also an empty one); with final == 0 the record
+ * left open at the file's end waits for the next call's text, as in `zcat a b`.  st->rows stays 0, st->frame_ms is the time of the
+ * mk_fql_* and carry kernels.  MK_ERR_FORMAT with st->bad_status: as above the status may come after text was pushed, so the caller
+ * finishes and drops the sketch, begins it anew and reads the file another way. */
+int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int final, mk_gunzip_stats *st);
 
 /* ---- a BATCH of single-member gzip genome files, many wavefronts per file ----------------------------------------
  * mk_sketch_batch_begin_gz with the decode above in place of one wavefront per file: a wave per span of S compressed bytes finds

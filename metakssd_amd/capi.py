@@ -179,6 +179,8 @@ def _load():
         "mk_sketch_push_wait": [vp, u64],
         "mk_sketch_push_stream": [vp, vp, u64, C.c_int],
         "mk_sketch_push_fastq_long": [vp, vp, u64, C.c_int],
+        "mk_sketch_push_fastq_long_device": [vp, vp, u64, C.c_int],
+        "mk_sketch_fastq_long_frame_ms": [vp, C.POINTER(C.c_double)],
         "mk_partial_count_begin": [vp],
         "mk_partial_export_async": [vp, vp, vp, vp, u64, C.POINTER(u64)],
         "mk_pack_rows_host": [vp, u32, u64, vp],
@@ -200,6 +202,7 @@ def _load():
                               C.POINTER(GunzipPiecesC)],
         "mk_inflate_stream_members": [vp, C.POINTER(u64)],
         "mk_sketch_push_gzip": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), u64, C.POINTER(GunzipStatsC)],
+        "mk_sketch_push_gzip_long": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), C.c_int, C.POINTER(GunzipStatsC)],
         "mk_sketch_push_gzip_q": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), i32, u64, C.POINTER(GunzipStatsC)],
         "mk_inflate_members": [vp, vp, C.c_size_t, C.POINTER(GzMemberC), u32, vp, C.c_size_t, C.POINTER(GzMemberResultC)],
         "mk_sketch_finish": [vp, C.POINTER(ResultC)],
@@ -299,6 +302,7 @@ def _load():
                                     C.POINTER(C.c_size_t), C.POINTER(u32)],
         "mk_inflate_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "mk_sketch_push_bgzf": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), u64, C.POINTER(BgzfStatsC)],
+        "mk_sketch_push_bgzf_long": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), C.c_int, C.POINTER(BgzfStatsC)],
         "mk_sketch_push_bgzf_q": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), i32, u64, C.POINTER(BgzfStatsC)],
     }
     for name, args in sig.items():
@@ -678,6 +682,48 @@ class Engine:
             at += n
             if last:
                 break
+
+    def push_fastq_long_device(self, dev_ptr, n, final=True):
+        """n bytes of FASTQ text at dev_ptr, in the memory of the engine's device, any alignment -> mk_sketch_push_fastq_long_device;
+        returns with the work queued: the memory stays untouched until the next call on this engine that waits"""
+        _check(lib.mk_sketch_push_fastq_long_device(self.h, C.c_void_p(dev_ptr) if n else None, n, 1 if final else 0), self.h)
+
+    def fastq_long_frame_ms(self):
+        """device milliseconds of the long-read framing kernels since begin() (mk_sketch_fastq_long_frame_ms)"""
+        ms = C.c_double(0)
+        _check(lib.mk_sketch_fastq_long_frame_ms(self.h, C.byref(ms)), self.h)
+        return ms.value
+
+    def push_gzip_long(self, path, span_bytes=0, ratio=0, batch_spans=0, members=False, final=True):
+        """a single-member gzip FASTQ file (members=True: a concatenation) into the MK_MODE_KOC sketch in progress by the long-read
+        rule (mk_sketch_push_gzip_long) -> GunzipStatsC; an inflate status raises MkError(MK_ERR_FORMAT) with the statistics in
+        .stats: the sketch is then to be finished, dropped and begun anew"""
+        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), GunzipStatsC()
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            rc = lib.mk_sketch_push_gzip_long(self.h, fd, os.fstat(fd).st_size, C.byref(o), 1 if final else 0, C.byref(st))
+        finally:
+            os.close(fd)
+        if rc:
+            err = MkError(rc, (lib.mk_bgzf_last_error() or b"").decode())
+            err.stats = st
+            raise err
+        return st
+
+    def push_bgzf_long(self, path, chunk_bytes=0, final=True):
+        """a BGZF-compressed FASTQ file into the MK_MODE_KOC sketch in progress by the long-read rule (mk_sketch_push_bgzf_long) ->
+        BgzfStatsC; a damaged member raises MkError(MK_ERR_FORMAT) with the statistics in .stats"""
+        o, st = BgzfOptsC(chunk_bytes, 0), BgzfStatsC()
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            rc = lib.mk_sketch_push_bgzf_long(self.h, fd, os.fstat(fd).st_size, C.byref(o), 1 if final else 0, C.byref(st))
+        finally:
+            os.close(fd)
+        if rc:
+            err = MkError(rc, (lib.mk_bgzf_last_error() or b"").decode())
+            err.stats = st
+            raise err
+        return st
 
     def push_reads_async(self, rows, stride, first_read_ordinal=0):
         """queue the copies and the scan; `rows` (host numpy u8) must stay untouched until push_wait(ticket)"""

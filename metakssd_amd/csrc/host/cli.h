@@ -103,6 +103,10 @@ typedef struct {
   int long_reads;          /* --long-reads: dist -A on FASTQ lines of any length -- the file's text goes to the device as it is and the sequence
                             * lines of complete records are scanned from the base stream (mk_sketch_push_fastq_long).  Opt-in:
                             * without the switch a line of 4 095+ characters is refused as before */
+  int long_inflate;        /* --long-inflate (implies --long-reads): a .gz input of that route is inflated on the device and its text goes from HBM
+                            * to the long-read framing -- a BGZF chain by mk_sketch_push_bgzf_long, another single gzip stream by
+                            * mk_sketch_push_gzip_long; everything else reads as under --long-reads.  A switch of its own because
+                            * --long-reads refuses --device-inflate and --device-gunzip, which name the short-read framing */
   int device_inflate_given; /* --device-inflate was on the command line (what --long-reads refuses) */
   mk_gunzip_opts gunzip_opts;   /* --gunzip-span-bytes, --gunzip-ratio, --gunzip-batch-spans (test hooks; 0 = the library's defaults) */
   uint64_t inflate_chunk_bytes; /* --inflate-chunk-kib: text bytes per chunk of the device route (test hook; 0 = the library's default) */

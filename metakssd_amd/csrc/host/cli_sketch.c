@@ -606,6 +606,13 @@ static size_t long_read_plain(int fd, uint8_t *dst, off_t off, size_t want, int 
   }
   return have;
 }
+static void report_long(const char *path, unsigned long long pieces, unsigned long long bytes, double t_in) {
+  if (!g_opt.timing) return;
+  char fb[160] = "";
+  if (g_gz_fallback) snprintf(fb, sizeof fb, ", \"fallback\": \"%s\"", g_gz_fallback);
+  printf("{\"input\": \"%s\", \"route\": \"long-reads\", \"source\": \"%s\", \"pieces\": %llu, \"text_bytes\": %llu, \"route_total_s\": %.4f%s}\n", path,
+         is_compressed(path) ? "zcat" : "file", pieces, bytes, now_s() - t_in, fb);
+}
 static void sketch_fastq_long(ctx_t *c, const char *path) {
   for (int k = 0; k < 2; k++)
     if (!c->long_buf[k] && mk_host_alloc((void **)&c->long_buf[k], LONG_CHUNK) != MK_OK) die("out of memory");
@@ -628,14 +635,78 @@ static void sketch_fastq_long(ctx_t *c, const char *path) {
     if (have < LONG_CHUNK) break;
   }
   CHECK(e, mk_sketch_push_fastq_long(e, NULL, 0, 1));
+  /* --long-inflate: the device route had the file first and gave it up with a status.  The line then comes in front of the wait for
+   * zcat, which may call the file damaged and end the run: why the file came this way is said either way */
+  if (g_gz_fallback) report_long(path, pieces, bytes, t_in);
   close_input(&in);
   c->t_last_push = now_s() - g_t0;
-  if (g_opt.timing)
-    printf("{\"input\": \"%s\", \"route\": \"long-reads\", \"source\": \"%s\", \"pieces\": %llu, \"text_bytes\": %llu, \"route_total_s\": %.4f}\n", path,
-           is_compressed(path) ? "zcat" : "file", pieces, bytes, now_s() - t_in);
+  if (!g_gz_fallback) report_long(path, pieces, bytes, t_in);
+}
+/* --long-inflate: a .gz of the long-read route is inflated on the device and its text goes from HBM to the same framing.
+ * A BGZF chain takes mk_sketch_push_bgzf_long, another file that mk_gzip_scan_stream calls single takes mk_sketch_push_gzip_long; 0:
+ * neither, or the gzip route gave the file up with a status -- what was pushed is then finished and dropped and the caller reads the
+ * file from its start through sketch_fastq_long (`zcat -fc`), which alone decides whether it is damaged.  A damaged BGZF block ends
+ * the run with sketch_fastq_bgzf's message.  One file is one sketch here, so every call closes the stream (final). */
+static int sketch_fastq_long_inflate(ctx_t *c, const char *path) {
+  if (!g_opt.long_inflate || !c->bgzf_ok || g_opt.no_device_inflate || !has_suffix(path, ".gz")) return 0;
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return 0;
+  struct stat st;
+  if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size == 0) { close(fd); return 0; }
+  const double t_in = now_s();
+  mk_bgzf_block *tab = NULL;
+  uint64_t nb = 0, total = 0;
+  int is_bgzf = 0;
+  if (mk_bgzf_scan(fd, NULL, (size_t)st.st_size, &tab, &nb, &total, &is_bgzf) == MK_OK && is_bgzf) {
+    mk_bgzf_free(tab);
+    mk_engine *e = sketch_engine(c);
+    if (c->t_first_push == 0) c->t_first_push = now_s() - g_t0;
+    mk_bgzf_opts o;
+    memset(&o, 0, sizeof o);
+    o.chunk_bytes = g_opt.inflate_chunk_bytes;
+    mk_bgzf_stats bs;
+    const int rc = mk_sketch_push_bgzf_long(e, fd, (size_t)st.st_size, &o, 1, &bs);
+    close(fd);
+    if (rc == MK_ERR_FORMAT && bs.bad_block >= 0)
+      die("%s: BGZF block %lld is damaged (%s): the input was not read completely", path, (long long)bs.bad_block, mk_inflate_status_text(bs.bad_status));
+    if (rc != MK_OK) die("mk_sketch_push_bgzf_long failed (%d): %s", rc, mk_bgzf_last_error());
+    c->t_last_push = now_s() - g_t0;
+    if (g_opt.timing)
+      printf("{\"input\": \"%s\", \"route\": \"long-reads\", \"source\": \"device-inflate\", \"blocks\": %llu, \"chunks\": %llu, \"comp_bytes\": %llu, "
+             "\"text_bytes\": %llu, \"inflate_ms\": %.3f, \"frame_ms\": %.3f, \"bgzf_scan_s\": %.4f, \"read_s\": %.4f, \"route_total_s\": %.4f}\n",
+             path, (unsigned long long)bs.blocks, (unsigned long long)bs.chunks, (unsigned long long)bs.comp_bytes, (unsigned long long)bs.text_bytes,
+             bs.inflate_ms, bs.frame_ms, bs.t_scan_s, bs.t_read_s, now_s() - t_in);
+    return 1;
+  }
+  mk_gzip_info info;
+  if (mk_gzip_scan_stream(fd, NULL, (size_t)st.st_size, &info) != MK_OK || !info.is_single) { close(fd); return 0; }
+  mk_engine *e = sketch_engine(c);
+  if (c->t_first_push == 0) c->t_first_push = now_s() - g_t0;
+  mk_gunzip_stats gs;
+  const int rc = mk_sketch_push_gzip_long(e, fd, (size_t)st.st_size, &g_opt.gunzip_opts, 1, &gs);
+  close(fd);
+  if (rc == MK_ERR_FORMAT && gs.bad_status) {
+    drop_pushed_and_fall_back(c, e, mk_gunzip_status_text(gs.bad_status));
+    return 0;
+  }
+  if (rc != MK_OK) die("mk_sketch_push_gzip_long failed (%d): %s", rc, mk_bgzf_last_error());
+  c->t_last_push = now_s() - g_t0;
+  if (g_opt.timing) {
+    char members[48] = ""; /* --gunzip-members: how many the file had */
+    if (g_opt.gunzip_opts.flags & MK_GUNZIP_MEMBERS) snprintf(members, sizeof members, ", \"members\": %u", gs.members);
+    printf("{\"input\": \"%s\", \"route\": \"long-reads\", \"source\": \"device-gunzip\", \"pieces\": %llu, \"batches\": %llu, \"comp_bytes\": %llu, "
+           "\"text_bytes\": %llu, \"find_ms\": %.3f, \"decode_ms\": %.3f, \"resolve_ms\": %.3f, \"frame_ms\": %.3f, \"read_s\": %.4f, \"route_total_s\": %.4f%s}\n",
+           path, (unsigned long long)gs.pieces, (unsigned long long)gs.batches, (unsigned long long)gs.comp_bytes, (unsigned long long)gs.text_bytes,
+           gs.find_ms, gs.decode_ms, gs.resolve_ms, gs.frame_ms, gs.t_read_s, now_s() - t_in, members);
+  }
+  return 1;
 }
 static void sketch_fastq(ctx_t *c, const char *path) {
-  if (g_opt.long_reads && !c->occ) { sketch_fastq_long(c, path); return; }
+  if (g_opt.long_reads && !c->occ) {
+    if (!sketch_fastq_long_inflate(c, path)) sketch_fastq_long(c, path);
+    g_gz_fallback = NULL;
+    return;
+  }
   if (sketch_fastq_mapped(c, path)) return;
   if (sketch_fastq_bgzf(c, path)) return;
   if (sketch_fastq_gunzip(c, path)) return;

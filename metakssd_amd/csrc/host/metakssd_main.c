@@ -104,6 +104,7 @@ static void parse_dist_options(int argc, char **argv) {
      * the -n / -Q reader (4.12); the -A reader's BGZF route needs no switch.  The later of the two switches holds. */
     else if (!strcmp(argv[i], "--device-inflate")) { o->no_device_inflate = 0; o->gz_batches = 1; o->device_inflate_q = 1; o->device_inflate_given = 1; }
     else if (!strcmp(argv[i], "--long-reads")) o->long_reads = 1; /* dist -A: FASTQ lines of any length through the base stream */
+    else if (!strcmp(argv[i], "--long-inflate")) o->long_reads = o->long_inflate = 1; /* ... and a .gz inflated on the device in front of it */
     else if (!strcmp(argv[i], "--device-gunzip")) o->device_gunzip = 1; /* dist -A and dist -n / -Q: a single-member .gz FASTQ inflated on the device */
     else if (!strcmp(argv[i], "--gunzip-members")) o->gunzip_opts.flags |= MK_GUNZIP_MEMBERS; /* ... and a concatenation of members */
     else if (!strcmp(argv[i], "--gunzip-span-bytes") && more) o->gunzip_opts.span_bytes = (uint32_t)atoll(argv[++i]);
@@ -140,9 +141,11 @@ static int dist_dispatch(void) {
   strlist *args = &o->args;
   int stage2_after = 0;
   if (o->long_reads) { /* the long-read route: what it cannot do is said before the device is touched */
-    if (!o->abundance) die("--long-reads needs -A: it is the route of the counted sketch");
-    if (o->occ_given) die("--long-reads does not take -n or -Q: their reader frames lines of up to 19998 characters itself");
-    if (o->ndev) die("--long-reads works on one GPU: --device D, not --devices");
+    const char *sw = o->long_inflate ? "--long-inflate" : "--long-reads";
+    if (!o->abundance) die("%s needs -A: it is the route of the counted sketch", sw);
+    if (o->occ_given) die("%s does not take -n or -Q: their reader frames lines of up to 19998 characters itself", sw);
+    if (o->ndev) die("%s works on one GPU: --device D, not --devices", sw);
+    if ((o->device_inflate_given || o->device_gunzip) && o->long_inflate) die("--long-inflate chooses the device route itself: not --device-inflate or --device-gunzip");
     if (o->device_inflate_given || o->device_gunzip) die("--long-reads reads .gz files through zcat: not --device-inflate or --device-gunzip");
   }
   if (o->composite_db) { /* the fused route: what it cannot do is said before the device is touched */
@@ -194,6 +197,8 @@ int main(int argc, char **argv) {
   if (strcmp(argv[1], "dist") != 0) die("only `dist`, `set`, `composite`, `reverse` and `shuffle` are part of this build (got `%s`)", argv[1]);
   for (int i = 2; i < argc; i++)
     if (!strcmp(argv[i], "--byread")) {
+      for (int j = 2; j < argc; j++)
+        if (!strcmp(argv[j], "--long-inflate")) die("--long-inflate does not go with --byread: per-read sketches keep the framing contract");
       for (int j = 2; j < argc; j++)
         if (!strcmp(argv[j], "--long-reads")) die("--long-reads does not go with --byread: per-read sketches keep the framing contract");
       return cmd_dist_byread(argc - 2, argv + 2);

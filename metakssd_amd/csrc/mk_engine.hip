@@ -142,8 +142,13 @@ struct mk_engine {
   /* mk_sketch_push_fastq_long: the same buffers and state; summaries of their own, and the record left open behind the last push */
   mk_fql_sum *d_fq_sum = nullptr;
   size_t fq_sum_cap = 0;
-  std::vector<uint8_t> fq_carry; /* text behind the last complete record: goes in front of the next push's text */
+  uint8_t *d_fq_carry = nullptr; /* text behind the last complete record (mk_fql_carry_kernel): goes in front of the next push's text */
+  size_t fq_carry_cap = 0;
+  uint64_t fq_carry_len = 0;     /* its bytes, known from the settle on (total - consumed) */
   uint64_t fq_total = 0;         /* bytes in d_text of the push that has not been settled: carry + piece */
+  hipEvent_t ev_fq[2] = {nullptr, nullptr}; /* around the framing kernels of the push queued last (mk_sketch_fastq_long_frame_ms) */
+  bool fq_timed = false;
+  double fq_frame_ms = 0;
   bool fq_used = false, fq_pending = false; /* fq_pending: a non-final push is queued, its state has not been read back */
 
   /* batches of small inputs (mk_sketch_batch_begin / _end): three contexts, two batches in flight, the third holds the results
@@ -334,7 +339,8 @@ extern "C" int mk_engine_destroy(mk_engine *e) {
   if (e->ev_scan_post) hipEventDestroy(e->ev_scan_post);
   if (e->ev_res) hipEventDestroy(e->ev_res);
   hipFree(e->d_text); hipFree(e->d_stream); hipFree(e->d_stream_tmp); hipFree(e->d_fa_sum); hipFree(e->d_fa_state);
-  hipFree(e->d_fq_sum);
+  hipFree(e->d_fq_sum); hipFree(e->d_fq_carry);
+  for (hipEvent_t ev : e->ev_fq) if (ev) hipEventDestroy(ev);
   if (e->h_fa_state) hipHostFree(e->h_fa_state);
   for (int i = 0; i < MK_TICKETS; i++) if (e->ev_ticket[i]) hipEventDestroy(e->ev_ticket[i]);
   if (e->h_counters) hipHostFree(e->h_counters);
@@ -679,6 +685,7 @@ static int mk_poison_scratch(mk_engine *e) {
   if (e->d_stream_tmp) MK_HIP(e, mk_dev_repoison(e->d_stream_tmp, 8192, s));
   if (e->d_fa_sum) MK_HIP(e, mk_dev_repoison(e->d_fa_sum, e->fa_sum_cap * sizeof(mk_fa_sum), s));
   if (e->d_fq_sum) MK_HIP(e, mk_dev_repoison(e->d_fq_sum, e->fq_sum_cap * sizeof(mk_fql_sum), s));
+  if (e->d_fq_carry) MK_HIP(e, mk_dev_repoison(e->d_fq_carry, e->fq_carry_cap, s)); /* (an open record of a sketch that was never closed is dropped by the begin) */
   if (e->d_stage[0] && e->copy_stream == e->stream) /* (rows staged for a sketch that was never finished are dropped by the begin) */
     for (int i = 0; i < MK_REGIONS; i++) MK_HIP(e, mk_dev_repoison(e->d_stage[i], e->stage_bytes, s));
   return MK_OK;
@@ -992,7 +999,7 @@ extern "C" int mk_sketch_begin(mk_engine *e, int mode) {
   e->count_queued = false;
   e->D = 0;
   e->fa_used = false; e->fa_final = false; e->fa_tail = 0; e->fa_rows_done = 0; e->fa_pitch = 0;
-  e->fq_used = false; e->fq_pending = false; e->fq_carry.clear(); e->fq_total = 0;
+  e->fq_used = false; e->fq_pending = false; e->fq_carry_len = 0; e->fq_total = 0; e->fq_timed = false; e->fq_frame_ms = 0;
   return MK_OK;
 }
 
@@ -1484,9 +1491,21 @@ extern "C" int mk_sketch_push_stream(mk_engine *e, const uint8_t *text, uint64_t
  * mt_shortreads2koc() with FQ_LEN unbounded (iseq2comem.c:656-720): mk_fastq_long.hip.h keeps the sequence lines of complete records,
  * one '>' behind each, in the base stream mk_sketch_push_stream uses, and the scan kernel reads the same virtual rows out of it.
  * A record's bases must not be scanned before its fourth line has come (:673 drops the record otherwise), so the text behind the
- * last complete record of a push -- the open record -- is not emitted; it is read back and goes in front of the next push's text,
- * which therefore always starts at a record start.  A non-final push waits for the stream anyway (rows taken, stream tail); with
- * pinned text that wait is put off to the start of the next call, so the caller fills its next buffer beside this push's kernels. */
+ * last complete record of a push -- the open record -- is not emitted; mk_fql_carry_kernel moves it to a buffer of its own in HBM,
+ * and it goes in front of the next push's text, which therefore always starts at a record start.  Of the open record the host knows
+ * the length alone (total - consumed, from the state words it reads back anyway).  A non-final push waits for the stream (rows
+ * taken, stream tail, consumed); with pinned or device text that wait is put off to the start of the next call, so the caller
+ * fills its next buffer beside this push's kernels.  Host and device pushes share all of this and may alternate within a sketch. */
+static int mk_fql_frame_time(mk_engine *e) { /* the framing kernels of the push queued last: behind a wait for them */
+  if (!e->fq_timed) return MK_OK;
+  e->fq_timed = false;
+  float ms = 0.f;
+  MK_HIP(e, hipEventSynchronize(e->ev_fq[1]));
+  MK_HIP(e, hipEventElapsedTime(&ms, e->ev_fq[0], e->ev_fq[1]));
+  e->fq_frame_ms += ms;
+  return MK_OK;
+}
+
 static int mk_fql_settle(mk_engine *e) {
   if (!e->fq_pending) return MK_OK;
   e->fq_pending = false;
@@ -1495,21 +1514,29 @@ static int mk_fql_settle(mk_engine *e) {
   e->fa_rows_done += taken;
   e->fa_tail = len > taken * e->fa_pitch ? len - taken * e->fa_pitch : 0;
   if (e->fa_tail > 8192) return mk_fail(e, MK_ERR_HIP, "mk_sketch_push_fastq_long: stream tail of %llu bytes", (unsigned long long)e->fa_tail);
-  if (consumed > total || (consumed && consumed <= e->fq_carry.size()))
+  if (consumed > total || (consumed && consumed <= e->fq_carry_len))
     return mk_fail(e, MK_ERR_HIP, "mk_sketch_push_fastq_long: record end at %llu of %llu bytes", (unsigned long long)consumed, (unsigned long long)total);
-  /* d_text holds the old carry and the piece: what lies behind the last record end is the new carry (no record end: all of it) */
-  try { e->fq_carry.resize((size_t)(total - consumed)); } catch (...) { return mk_fail(e, MK_ERR_NOMEM, "mk_sketch_push_fastq_long: %llu bytes for an open record", (unsigned long long)(total - consumed)); }
-  if (total > consumed) {
-    MK_HIP(e, hipMemcpyAsync(e->fq_carry.data(), e->d_text + consumed, (size_t)(total - consumed), hipMemcpyDeviceToHost, e->stream));
-    MK_HIP(e, hipStreamSynchronize(e->stream));
-  }
-  return MK_OK;
+  /* d_text held the old carry and the piece: what lies behind the last record end is the new carry (no record end: all of it), and
+   * mk_fql_carry_kernel has moved it to d_fq_carry */
+  e->fq_carry_len = total - consumed;
+  return mk_fql_frame_time(e);
 }
 
-static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int final) {
-  const uint64_t c = e->fq_carry.size(), total = c + n;
-  int rc = mk_fa_reserve(e, (size_t)total);
+/* from_device: `text` lies in this device's memory and is copied on the engine's stream, nothing waits */
+static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int final, bool from_device) {
+  const uint64_t c = e->fq_carry_len, total = c + n;
+  int rc = mk_fa_reserve(e, (size_t)total); /* (a regrowth leaves d_fq_carry alone) */
   if (rc) return rc;
+  if (c) MK_HIP(e, hipMemcpyAsync(e->d_text, e->d_fq_carry, (size_t)c, hipMemcpyDeviceToDevice, e->stream));
+  if (!final && total + 16u > e->fq_carry_cap) { /* room for all of this push's text: grown before the kernel that fills it is queued */
+    MK_HIP(e, hipStreamSynchronize(e->stream)); /* (the copy above was the last reader of the old one) */
+    hipFree(e->d_fq_carry);
+    e->d_fq_carry = nullptr; e->fq_carry_cap = 0;
+    const size_t cap = (size_t)(total + total / 2 + ((size_t)1 << 20));
+    MK_HIP(e, mk_dev_alloc(&e->d_fq_carry, cap));
+    e->fq_carry_cap = cap;
+  }
+  if (!e->ev_fq[0]) for (hipEvent_t &ev : e->ev_fq) MK_HIP(e, hipEventCreate(&ev));
   const uint64_t nseg = (total + MK_FA_SEG - 1) / MK_FA_SEG;
   if (nseg > e->fq_sum_cap) {
     MK_HIP(e, hipStreamSynchronize(e->stream));
@@ -1523,20 +1550,25 @@ static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int 
   const uint32_t width = (rowlen + 1u + 15u) & ~15u;
   e->fa_used = true; e->fq_used = true;
   bool pinned = true;
-  if (n) {
+  if (n && !from_device) {
     hipPointerAttribute_t attr;
     pinned = hipPointerGetAttributes(&attr, text) == hipSuccess && attr.type == hipMemoryTypeHost;
     if (!pinned) (void)hipGetLastError();
   }
-  if (c) MK_HIP(e, hipMemcpyAsync(e->d_text, e->fq_carry.data(), (size_t)c, hipMemcpyHostToDevice, e->stream));
-  if (n) MK_HIP(e, hipMemcpyAsync(e->d_text + c, text, (size_t)n, hipMemcpyHostToDevice, e->stream));
-  if (c || !pinned) MK_HIP(e, hipStreamSynchronize(e->stream)); /* pageable memory (the carry is): free again when the call returns */
+  if (n) MK_HIP(e, hipMemcpyAsync(e->d_text + c, text, (size_t)n, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+  if (!pinned) MK_HIP(e, hipStreamSynchronize(e->stream)); /* pageable memory: free again when the call returns */
+  MK_HIP(e, hipEventRecord(e->ev_fq[0], e->stream));
   if (nseg) hipLaunchKernelGGL(mk_fql_summary_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text, total, e->d_fq_sum);
   hipLaunchKernelGGL(mk_fql_scan_kernel, dim3(1), dim3(1024), 0, e->stream, e->d_fq_sum, nseg, (const uint8_t *)e->d_text, total, e->d_fa_state,
                      e->d_stream, pitch, rowlen, TL, final ? 1 : 0);
   if (nseg) hipLaunchKernelGGL(mk_fql_emit_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text,
                                (const mk_fql_sum *)e->d_fq_sum, (const mk_fa_state *)e->d_fa_state, e->d_stream, (unsigned long long)e->fa_tail);
+  /* the open record leaves d_text before the next push rewrites it -- and before that push's scan kernel rewrites st->in_header */
+  if (!final && nseg) hipLaunchKernelGGL(mk_fql_carry_kernel, dim3(256), dim3(256), 0, e->stream, (const uint8_t *)e->d_text, total,
+                                         (const mk_fa_state *)e->d_fa_state, e->d_fq_carry);
   MK_HIP(e, hipGetLastError());
+  MK_HIP(e, hipEventRecord(e->ev_fq[1], e->stream));
+  e->fq_timed = true;
   const uint64_t ub_len = e->fa_tail + total; /* rows the launch is sized for: what the stream could hold at most */
   uint64_t ub_rows = 0;
   if (final) { if (ub_len >= TL) ub_rows = (ub_len - (TL - 1u) + pitch - 1u) / pitch; }
@@ -1545,7 +1577,7 @@ static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int 
     rc = mk_launch_scan_ex(e, e->d_stream, width, pitch, rowlen, ub_rows, &e->d_fa_state->nrows, e->fa_rows_done);
     if (rc) return rc;
   }
-  if (final) { e->fa_final = true; e->fq_carry.clear(); return MK_OK; }
+  if (final) { e->fa_final = true; e->fq_carry_len = 0; return MK_OK; }
   hipLaunchKernelGGL(mk_fa_shift_kernel, dim3(8), dim3(1024), 0, e->stream, e->d_stream, e->d_stream_tmp, e->d_fa_state, pitch, 0);
   hipLaunchKernelGGL(mk_fa_shift_kernel, dim3(8), dim3(1024), 0, e->stream, e->d_stream, e->d_stream_tmp, e->d_fa_state, pitch, 1);
   MK_HIP(e, hipMemcpyAsync(e->h_fa_state, e->d_fa_state, sizeof(mk_fa_state), hipMemcpyDeviceToHost, e->stream));
@@ -1556,26 +1588,51 @@ static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int 
   return pinned ? MK_OK : mk_fql_settle(e);
 }
 
-extern "C" int mk_sketch_push_fastq_long(mk_engine *e, const uint8_t *text, uint64_t n, int final) {
+static int mk_fql_push(mk_engine *e, const char *who, const uint8_t *text, uint64_t n, int final, bool from_device) {
   if (!e || (!text && n)) return MK_ERR_ARG;
   if (!e->begun) return mk_fail(e, MK_ERR_STATE, "push before mk_sketch_begin");
-  if (e->mode != MK_MODE_KOC) return mk_fail(e, MK_ERR_STATE, "mk_sketch_push_fastq_long: for MK_MODE_KOC sketches only");
-  if (e->fa_final) return mk_fail(e, MK_ERR_STATE, "mk_sketch_push_fastq_long: the stream has been closed (final) for this sketch");
-  if (e->fa_used && !e->fq_used) return mk_fail(e, MK_ERR_STATE, "mk_sketch_push_fastq_long: this sketch has taken FASTA text (mk_sketch_push_stream)");
-  if (n >= (1ull << 31)) return mk_fail(e, MK_ERR_ARG, "mk_sketch_push_fastq_long: at most 2^31 - 1 bytes per call");
-  if (e->P.TL + MK_FA_PITCH > 4000u) return mk_fail(e, MK_ERR_ARG, "mk_sketch_push_fastq_long: k-mer too long for the stream rows");
+  if (e->mode != MK_MODE_KOC) return mk_fail(e, MK_ERR_STATE, "%s: for MK_MODE_KOC sketches only", who);
+  if (e->fa_final) return mk_fail(e, MK_ERR_STATE, "%s: the stream has been closed (final) for this sketch", who);
+  if (e->fa_used && !e->fq_used) return mk_fail(e, MK_ERR_STATE, "%s: this sketch has taken FASTA text (mk_sketch_push_stream)", who);
+  if (n >= (1ull << 31)) return mk_fail(e, MK_ERR_ARG, "%s: at most 2^31 - 1 bytes per call", who);
+  if (e->P.TL + MK_FA_PITCH > 4000u) return mk_fail(e, MK_ERR_ARG, "%s: k-mer too long for the stream rows", who);
   MK_HIP(e, hipSetDevice(e->device));
+  if (from_device && n) { /* a host pointer would be read as one by the copy and land as garbage, or fault */
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, text) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != e->device) {
+      (void)hipGetLastError();
+      return mk_fail(e, MK_ERR_ARG, "%s: the text is not in the memory of device %d", who, e->device);
+    }
+  }
   { int rc = mk_flush_region(e); if (rc) return rc; }
   for (;;) {
     int rc = mk_fql_settle(e);
     if (rc) return rc;
     /* open record + piece go through the kernels as one text of less than 2^31 bytes */
-    const uint64_t room = ((1ull << 31) - 1u) - e->fq_carry.size();
-    if (n <= room) return mk_fql_push_piece(e, text, n, final);
-    if (!room) return mk_fail(e, MK_ERR_ARG, "mk_sketch_push_fastq_long: a record of 2^31 bytes or more");
-    if ((rc = mk_fql_push_piece(e, text, room, 0))) return rc;
+    const uint64_t room = ((1ull << 31) - 1u) - e->fq_carry_len;
+    if (n <= room) return mk_fql_push_piece(e, text, n, final, from_device);
+    if (!room) return mk_fail(e, MK_ERR_ARG, "%s: a record of 2^31 bytes or more", who);
+    if ((rc = mk_fql_push_piece(e, text, room, 0, from_device))) return rc;
     text += room; n -= room;
   }
+}
+
+extern "C" int mk_sketch_push_fastq_long(mk_engine *e, const uint8_t *text, uint64_t n, int final) {
+  return mk_fql_push(e, "mk_sketch_push_fastq_long", text, n, final, false);
+}
+
+/* the same for text in this device's memory, at any alignment: copied behind the open record on the engine's stream, so the
+ * caller's buffer is free once work queued later on that stream may overwrite it; returns with its work queued */
+extern "C" int mk_sketch_push_fastq_long_device(mk_engine *e, const uint8_t *d_text, uint64_t n, int final) {
+  return mk_fql_push(e, "mk_sketch_push_fastq_long_device", d_text, n, final, true);
+}
+
+extern "C" int mk_sketch_fastq_long_frame_ms(mk_engine *e, double *ms) {
+  if (!e || !ms) return MK_ERR_ARG;
+  MK_HIP(e, hipSetDevice(e->device));
+  { int rc = mk_fql_frame_time(e); if (rc) return rc; }
+  *ms = e->fq_frame_ms;
+  return MK_OK;
 }
 
 /* ---- compaction / partials --------------------------------------------------------------------------- */

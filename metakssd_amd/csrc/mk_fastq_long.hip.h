@@ -14,12 +14,13 @@
  * the summaries is two plain prefix sums: newlines (-> entry role of every segment), then the kept bytes for that role.
  *
  * Record rule (:673): a record counts when its fourth fgets() gives at least one byte.  The text of one push always starts at a record
- * start (the host carries the open record in front of the next push's text, mk_engine.hip), so with N newlines in the push the last
+ * start (the engine puts the open record in front of the next push's text, mk_engine.hip), so with N newlines in the push the last
  * record ends behind newline number 4 * (N / 4); the scan kernel finds that byte (`consumed`), the emit kernel stops there.  The
  * final push also takes a last record whose quality line has bytes but no '\n' (N mod 4 == 3, last byte no '\n').
  *   mk_fql_summary_kernel  one wave per segment of MK_FA_SEG bytes
  *   mk_fql_scan_kernel     one workgroup: prefix sums, the cut, stream length and row count (as mk_fa_scan_kernel)
  *   mk_fql_emit_kernel     the same walk with the entry role known: kept bytes to stream[offset ..], up to the cut
+ *   mk_fql_carry_kernel    the text behind the cut (the open record) to the engine's carry buffer: it never leaves HBM
  */
 #pragma once
 #include "mk_stream.hip.h"
@@ -197,5 +198,30 @@ __global__ void __launch_bounds__(256) mk_fql_emit_kernel(const uint8_t *text, c
     const uint64_t keep = mk_fql_step(ch, valid, lane, role);
     if ((keep >> lane) & 1ull) stream[off + mk_mbcnt(keep)] = ch == (uint8_t)'\n' ? (uint8_t)'>' : ch;
     off += (uint64_t)__popcll(keep);
+  }
+}
+
+/* The open record stays in HBM: text[consumed, total) -> carry[0, total - consumed), with consumed = st->in_header as mk_fql_scan_kernel
+ * left it (queued behind mk_fql_emit_kernel, in front of the next push's scan kernel, the only thing that rewrites that word).  `carry`
+ * is a buffer of its own: the carry is longer than `consumed` as soon as a record spans three pushes, and a move to the front of `text`
+ * would then read what other threads have overwritten.  The source starts anywhere, the destination is aligned: a thread gives one
+ * 16-byte store from two aligned 16-byte loads, the second only where it starts in front of `total` (whole 16-byte pieces of the text
+ * buffer up to there exist: it is allocated in whole segments); carry holds total + 16 bytes at least.  A fixed grid and a stride: the
+ * carry is one record as a rule. */
+__global__ void __launch_bounds__(256) mk_fql_carry_kernel(const uint8_t *text, uint64_t total, const mk_fa_state *st, uint8_t *carry) {
+  const uint64_t consumed = st->in_header;
+  if (consumed >= total) return;
+  const uint64_t base = consumed & ~(uint64_t)15u, nvec = (total - consumed + 15u) >> 4;
+  const uint32_t s = (uint32_t)(consumed & 15u), r = 8u * (s & 7u);
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t at = base + 16u * i;
+    const uint4 a = *(const uint4 *)(text + at);
+    uint4 b = make_uint4(0u, 0u, 0u, 0u);
+    if (s && at + 16u < total) b = *(const uint4 *)(text + at + 16u);
+    uint64_t v0 = (uint64_t)a.y << 32 | a.x, v1 = (uint64_t)a.w << 32 | a.z, v2 = (uint64_t)b.y << 32 | b.x;
+    const uint64_t v3 = (uint64_t)b.w << 32 | b.z;
+    if (s >= 8u) { v0 = v1; v1 = v2; v2 = v3; }
+    const uint64_t o0 = r ? v0 >> r | v1 << (64u - r) : v0, o1 = r ? v1 >> r | v2 << (64u - r) : v1;
+    *(uint4 *)(carry + 16u * i) = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
   }
 }

@@ -915,6 +915,69 @@ static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts 
   return MK_OK;
 }
 
+/* The long sink: the same stream decode, every batch's text to mk_sketch_push_fastq_long_device.  The engine copies
+ * the text into its own buffer on R.S, which is its stream, so R.d_text is free for the next batch's resolve; the open record waits
+ * in the engine.  No framer, no carry of this route's, no slices: a batch holds less than 2^31 bytes of text. */
+extern "C" int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int final, mk_gunzip_stats *st) {
+  if (!e || fd < 0) return MK_ERR_ARG;
+  mk_gunzip_stats stats;
+  memset(&stats, 0, sizeof stats);
+  stats.bad_piece = -1;
+  if (st) *st = stats;
+  const double t_begin = mk_now_s();
+  mk_gzip_info info;
+  int rc = mk_gzip_scan_stream(fd, nullptr, size, &info);
+  if (rc) return rc;
+  if (!info.is_single) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "not a single-member gzip file"); return MK_ERR_ARG; }
+  void *sp = nullptr;
+  int device = 0;
+  rc = mk_engine_get_stream(e, &sp, &device);
+  if (rc) return rc;
+  mk_gun_run R;
+  R.S = (hipStream_t)sp;
+  MK_GUN_HIP(hipSetDevice(device));
+  double frame0 = 0;
+  if ((rc = mk_sketch_fastq_long_frame_ms(e, &frame0))) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
+  auto read = [&](uint64_t off, uint64_t n, uint8_t *dst) -> int {
+    for (uint64_t got = 0; got < n;) {
+      const ssize_t r = pread(fd, dst + got, n - got, (off_t)(off + got));
+      if (r <= 0) return MK_ERR_IO;
+      got += (uint64_t)r;
+    }
+    return MK_OK;
+  };
+  bool closed = false;
+  auto sink = [&](uint8_t *d_text, uint64_t n, bool final_batch) -> int {
+    const int fin = final && final_batch;
+    if (n == 0 && !fin) return MK_OK;
+    const int prc = mk_sketch_push_fastq_long_device(e, d_text + MK_FQ_CARRY, n, fin);
+    if (prc) snprintf(R.err, sizeof R.err, "%s", mk_last_error(e));
+    else if (fin) closed = true;
+    return prc;
+  };
+  mk_gun_result res;
+  rc = mk_gun_stream(R, size, info, opts, read, sink, nullptr, res);
+  if (!rc && !res.status && final && !closed) { /* (no batch called itself the last one: the stream had no piece to give) */
+    rc = mk_sketch_push_fastq_long_device(e, nullptr, 0, 1);
+    if (rc) snprintf(R.err, sizeof R.err, "%s", mk_last_error(e));
+  }
+  (void)hipStreamSynchronize(R.S);
+  double frame1 = frame0;
+  (void)mk_sketch_fastq_long_frame_ms(e, &frame1);
+  stats.frame_ms = frame1 - frame0;
+  stats.pieces = res.npieces; stats.batches = res.nbatches; stats.comp_bytes = size; stats.text_bytes = res.text_len;
+  stats.find_ms = res.find_ms; stats.decode_ms = res.decode_ms; stats.resolve_ms = res.resolve_ms; stats.t_read_s = res.t_read_s;
+  stats.bad_piece = res.bad_piece; stats.bad_status = res.status; stats.members = (uint32_t)std::min<uint64_t>(res.members, 0xffffffffu);
+  stats.t_total_s = mk_now_s() - t_begin;
+  if (st) *st = stats;
+  if (rc) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", R.err); return rc; }
+  if (res.status) {
+    snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "gzip stream, piece %lld: %s", (long long)res.bad_piece, mk_gunzip_status_text(res.status));
+    return MK_ERR_FORMAT;
+  }
+  return MK_OK;
+}
+
 extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, uint64_t first_ordinal, mk_gunzip_stats *st) {
   return mk_push_gzip(e, fd, size, opts, false, 0, first_ordinal, st);
 }

@@ -26,6 +26,9 @@
  *                        markers, window chain, resolve -- around this file's bit reader, table builder and CRC kernels.
  * mk_gunzip_batch.hip.h (behind it): a BATCH of gzip genome files, many waves per file, as one launch sequence without a host wait:
  *                        the same finder and decode per (file, span), the piece table and the text offsets made on the device (4.16).
+ * The long sinks (mk_sketch_push_bgzf_long here, mk_sketch_push_gzip_long in mk_gunzip.hip.h) reuse the inflate side of
+ *                        both routes and hand the text to mk_sketch_push_fastq_long_device instead of the framer; mk_bgzf_bad_kernel
+ *                        reduces a chunk's member statuses where the framer's scan kernel did.
  * Bound of each kernel: DESIGN.md 4.10, 4.12.
  */
 #include <hip/hip_runtime.h>
@@ -743,6 +746,8 @@ struct mk_bgzf_run { /* everything mk_sketch_push_bgzf allocates beside its fram
   hipStream_t copy = nullptr;
   uint8_t *h_stage[2] = {nullptr, nullptr}, *d_comp[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr};
   uint32_t *d_status[2] = {nullptr, nullptr};
+  uint32_t *d_bad = nullptr, *h_bad = nullptr; /* the long sink: mk_bgzf_bad_kernel's two words and their pinned mirror */
+  hipEvent_t ev_bad = nullptr;
   hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_i[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
   ~mk_bgzf_run() {
     mk_bgzf_free(blocks);
@@ -752,10 +757,24 @@ struct mk_bgzf_run { /* everything mk_sketch_push_bgzf allocates beside its fram
       if (ev_up[s]) (void)hipEventDestroy(ev_up[s]);
       for (int k = 0; k < 2; k++) if (ev_i[s][k]) (void)hipEventDestroy(ev_i[s][k]);
     }
+    (void)hipFree(d_bad);
+    if (h_bad) (void)hipHostFree(h_bad);
+    if (ev_bad) (void)hipEventDestroy(ev_bad);
     if (copy) (void)hipStreamDestroy(copy);
   }
 };
 struct mk_bgzf_chunk { uint64_t b0, b1, in0, in1, text; };
+
+/* the long sink has no framer whose scan kernel reduces the members' statuses: one workgroup does that alone.
+ * out[0] := the first member of the chunk with a status (0xffffffff: none), out[1] := that status */
+__global__ void __launch_bounds__(1024) mk_bgzf_bad_kernel(const uint32_t *status, uint32_t nblocks, uint32_t *out) {
+  __shared__ uint32_t s_bad;
+  if (threadIdx.x == 0u) s_bad = 0xffffffffu;
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < nblocks; i += 1024u) if (status[i]) atomicMin(&s_bad, i);
+  __syncthreads();
+  if (threadIdx.x == 0u) { out[0] = s_bad; out[1] = s_bad != 0xffffffffu ? status[s_bad] : 0u; }
+}
 }
 
 static thread_local char mk_bgzf_err[256];
@@ -765,8 +784,11 @@ static thread_local char mk_bgzf_err[256];
     if (_r != hipSuccess) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s: %s", #call, hipGetErrorString(_r)); (void)hipStreamSynchronize(S); if (R.copy) (void)hipStreamSynchronize(R.copy); return MK_ERR_HIP; } \
   } while (0)
 
-/* both readers' route: occ == false is mk_fastq_frame's rule (-A), occ == true mk_fastq_frame_q's (quality mask qmin) */
-static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, bool occ, int32_t qmin, uint64_t first_ordinal, mk_bgzf_stats *st) {
+/* both readers' route: occ == false is mk_fastq_frame's rule (-A), occ == true mk_fastq_frame_q's (quality mask qmin).  lng: the long
+ * sink -- scan, chunks, upload and inflate are the same; a chunk's text goes to mk_sketch_push_fastq_long_device
+ * instead of the framer, `final` with the file's last chunk when final_in says the sketch ends with this file. */
+static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, bool occ, int32_t qmin, uint64_t first_ordinal, mk_bgzf_stats *st,
+                        bool lng = false, int final_in = 1) {
   if (!e || fd < 0) return MK_ERR_ARG;
   mk_bgzf_stats stats;
   memset(&stats, 0, sizeof stats);
@@ -817,8 +839,16 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
     for (int k = 0; k < 2; k++) MK_BGZF_HIP(hipEventCreate(&R.ev_i[s][k]));
   }
   mk_fq_framer F;
-  MK_BGZF_HIP(F.setup(occ, qmin));
-  MK_BGZF_HIP(F.reserve(S, MK_FQ_CARRY + max_text, rows_bytes));
+  double frame0 = 0;
+  if (lng) {
+    MK_BGZF_HIP(mk_dev_alloc(&R.d_bad, 2 * sizeof(uint32_t)));
+    MK_BGZF_HIP(mk_pin_alloc(&R.h_bad, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    MK_BGZF_HIP(hipEventCreateWithFlags(&R.ev_bad, hipEventDisableTiming));
+    if ((rc = mk_sketch_fastq_long_frame_ms(e, &frame0))) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
+  } else {
+    MK_BGZF_HIP(F.setup(occ, qmin));
+    MK_BGZF_HIP(F.reserve(S, MK_FQ_CARRY + max_text, rows_bytes));
+  }
 
   /* chunk k: file -> pinned staging -> device (copy stream), inflate behind it on the engine's stream */
   auto queue_inflate = [&](size_t k) -> int {
@@ -847,6 +877,12 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
     return MK_OK;
   };
 
+  if (lng && chunks.empty()) { /* (a file without a member has no text) */
+    if (final_in && (rc = mk_sketch_push_fastq_long_device(e, nullptr, 0, 1))) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
+    stats.comp_bytes = size; stats.t_total_s = mk_now_s() - t_begin;
+    if (st) *st = stats;
+    return MK_OK;
+  }
   rc = queue_inflate(0);
   if (rc) return rc;
   uint32_t carry = 0;
@@ -859,6 +895,29 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
   for (size_t k = 0; k < chunks.size(); k++) {
     const mk_bgzf_chunk &c = chunks[k];
     const int s = (int)(k & 1u), final = k + 1 == chunks.size();
+    if (lng) {
+      hipLaunchKernelGGL(mk_bgzf_bad_kernel, dim3(1), dim3(1024), 0, S, (const uint32_t *)R.d_status[s], (uint32_t)(c.b1 - c.b0), R.d_bad);
+      MK_BGZF_HIP(hipGetLastError());
+      MK_BGZF_HIP(hipMemcpyAsync(R.h_bad, R.d_bad, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, S));
+      MK_BGZF_HIP(hipEventRecord(R.ev_bad, S));
+      if (!final) { /* the next chunk's bytes travel beside this one's framing and scan; its text buffer was chunk k - 1's, which the engine has copied out of on S */
+        rc = queue_inflate(k + 1);
+        if (rc) return rc;
+      }
+      MK_BGZF_HIP(hipEventSynchronize(R.ev_bad)); /* the one wait per chunk */
+      MK_BGZF_HIP(hipEventElapsedTime(&ms, R.ev_i[s][0], R.ev_i[s][1]));
+      stats.inflate_ms += ms;
+      if (R.h_bad[0] != 0xffffffffu) {
+        stats.bad_block = (int64_t)(c.b0 + R.h_bad[0]);
+        stats.bad_status = (int32_t)R.h_bad[1];
+        snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "BGZF block %llu: %s", (unsigned long long)stats.bad_block, mk_inflate_status_text(stats.bad_status));
+        result = MK_ERR_FORMAT;
+        break;
+      }
+      rc = mk_sketch_push_fastq_long_device(e, R.d_text[s] + MK_FQ_CARRY, c.text, final_in && final);
+      if (rc) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
+      continue;
+    }
     const uint32_t t0 = MK_FQ_CARRY - carry, e1 = MK_FQ_CARRY + (uint32_t)c.text;
     MK_BGZF_HIP(F.count(S, R.d_text[s], t0, e1, final, R.d_status[s], (uint32_t)(c.b1 - c.b0)));
     if (!final) { /* the next chunk's bytes travel and inflate beside this one's framing and scan (its slots were chunk k - 1's, whose read-back has been waited for) */
@@ -894,8 +953,14 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
   }
   MK_BGZF_HIP(hipStreamSynchronize(S));
   MK_BGZF_HIP(hipStreamSynchronize(R.copy));
-  MK_BGZF_HIP(F.times(&ms, &rows_ms));
-  stats.frame_ms += rows_ms;
+  if (lng) {
+    double frame1 = frame0;
+    (void)mk_sketch_fastq_long_frame_ms(e, &frame1);
+    stats.frame_ms = frame1 - frame0;
+  } else {
+    MK_BGZF_HIP(F.times(&ms, &rows_ms));
+    stats.frame_ms += rows_ms;
+  }
   stats.blocks = nblocks; stats.chunks = chunks.size(); stats.comp_bytes = size; stats.text_bytes = total;
   stats.t_total_s = mk_now_s() - t_begin;
   if (st) *st = stats;
@@ -908,6 +973,10 @@ extern "C" int mk_sketch_push_bgzf(mk_engine *e, int fd, size_t size, const mk_b
 
 extern "C" int mk_sketch_push_bgzf_q(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int32_t qmin, uint64_t first_ordinal, mk_bgzf_stats *st) {
   return mk_push_bgzf(e, fd, size, o, true, qmin, first_ordinal, st);
+}
+
+extern "C" int mk_sketch_push_bgzf_long(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int final, mk_bgzf_stats *st) {
+  return mk_push_bgzf(e, fd, size, o, false, 0, 0, st, true, final);
 }
 
 extern "C" const char *mk_bgzf_last_error(void) { return mk_bgzf_err; }

@@ -95,6 +95,107 @@ def kernel_totals(directory, name):
     return out
 
 
+def write_compressed(tmp, fq):
+    """the long FASTQ three ways, written side by side: one gzip member at level 1, one at level 6, BGZF (`bgzip` where the machine
+    has it, else members of 65 280 text bytes by tests/bgzf_util.py's writer) -> {name: path}, {name: how it was written}"""
+    import bgzf_util as bu
+    paths = {"gzip1": os.path.join(tmp, "long_l1.fq.gz"), "gzip6": os.path.join(tmp, "long_l6.fq.gz"), "bgzf": os.path.join(tmp, "long_bgzf.fq.gz")}
+    how = {"gzip1": "gzip -1", "gzip6": "gzip -6"}
+    procs = [subprocess.Popen(["gzip", "-%d" % lv, "-n", "-c", fq], stdout=open(paths[k], "wb")) for k, lv in (("gzip1", 1), ("gzip6", 6))]
+    if shutil.which("bgzip"):
+        how["bgzf"] = "bgzip"
+        procs.append(subprocess.Popen(["bgzip", "-c", fq], stdout=open(paths["bgzf"], "wb")))
+    else:
+        how["bgzf"] = "tests/bgzf_util.py member(), 65 280 text bytes a member, level 6"
+        with open(fq, "rb") as src, open(paths["bgzf"], "wb") as dst:
+            while True:
+                piece = src.read(65280)
+                if not piece:
+                    break
+                dst.write(bu.member(piece, 6))
+            dst.write(bu.EOF_MARKER)
+    for p in procs:
+        if p.wait() != 0:
+            raise RuntimeError("writing a compressed input failed")
+    return paths, how
+
+
+def spread(walls):
+    return {"wall_s": round(statistics.median(walls), 4), "wall_min_s": round(min(walls), 4), "wall_max_s": round(max(walls), 4), "wall_runs": [round(v, 4) for v in walls]}
+
+
+def main_gz(a):
+    """--gz: the long FASTQ compressed three ways; per file the parent's `dist -A --long-reads` (its zcat child) against
+    this build's `dist -A --long-inflate`, and the plain file through `--long-reads` of both builds (the carry moved to the device)."""
+    from golden_cases import make_shuf
+    if not a.parent_cli:
+        raise SystemExit("--gz needs --parent-cli: the legs it is measured against are the parent commit's")
+    tmp = tempfile.mkdtemp(prefix="bench_longreads_gz_", dir=a.tmp)
+    try:
+        shuf = os.path.join(tmp, "L3K11.shuf")
+        make_shuf("L3K11", shuf)
+        t0 = time.perf_counter()
+        fq, chopped, fa, nreads, bases = write_inputs(tmp, a.gbases, a.read_len, 22, False)
+        os.remove(chopped)
+        os.remove(fa)
+        files, how = write_compressed(tmp, fq)
+        files["plain"] = fq
+        write_s = time.perf_counter() - t0
+        for p in files.values():  # into the page cache
+            with open(p, "rb") as f:
+                while f.read(64 << 20):
+                    pass
+        want_source = {"gzip1": "device-gunzip", "gzip6": "device-gunzip", "bgzf": "device-inflate", "plain": "file"}
+        legs = {}
+        for k, p in files.items():
+            legs[k + "/parent"] = [a.parent_cli, "dist", "-L", shuf, "-A", "--long-reads", "--quiet", "--timing", "-o", os.path.join(tmp, "out_parent_" + k), p]
+            legs[k + "/this"] = [CLI, "dist", "-L", shuf, "-A", "--long-reads" if k == "plain" else "--long-inflate", "--quiet", "--timing", "-o",
+                                 os.path.join(tmp, "out_this_" + k), p]
+        walls, infos, want = {k: [] for k in legs}, {}, None
+        for r in range(a.runs):
+            for k, cmd in legs.items():  # taking turns: a drift of the machine hits all legs alike
+                shutil.rmtree(cmd[-2], ignore_errors=True)
+                dt, infos[k] = run(cmd)
+                got = combco(cmd[-2])
+                want = want or got
+                if not got or got != want:  # before a time is kept
+                    raise RuntimeError("run %d, leg %s: its directory differs from the first leg's" % (r, k))
+                if k.endswith("/this") and (infos[k].get("source") != want_source[k.split("/")[0]] or "fallback" in infos[k]):
+                    raise RuntimeError("run %d, leg %s: the route was not taken (%s)" % (r, k, infos[k]))
+                walls[k].append(dt)
+            print("run %d: %s" % (r, {k: round(v[-1], 3) for k, v in walls.items()}), file=sys.stderr, flush=True)
+        keys = sum(len(v) for n, v in want.items() if not n.endswith(".a") and ".index." not in n) // 4
+        res = {"bench": "longreads_gz", "what": "wall seconds from process start to exit (directory on disk): dist -A --long-reads of the parent commit (zcat child for a "
+               ".gz) against dist -A --long-inflate of this build on the same file, reads of %d bases, L3K11, median of %d runs, the legs taking turns, files in the "
+               "page cache; plain: dist -A --long-reads of both builds on the uncompressed file" % (a.read_len, a.runs),
+               "reads": nreads, "bases": bases, "read_len": a.read_len, "runs": a.runs, "keys": keys, "directories_equal": True, "writing_the_files_s": round(write_s, 1),
+               "written_by": how, "file_bytes": {k: os.path.getsize(p) for k, p in files.items()}, "inputs": {}}
+        for k in files:
+            p, t = spread(walls[k + "/parent"]), spread(walls[k + "/this"])
+            route = {f: v for f, v in infos[k + "/this"].items() if f not in ("input", "timing")}
+            res["inputs"][k] = {"parent": p, "this": t, "gbases_s": {"parent": round(bases / p["wall_s"] / 1e9, 3), "this": round(bases / t["wall_s"] / 1e9, 3)},
+                                "ratio_parent_over_this": round(p["wall_s"] / t["wall_s"], 3),
+                                "outside_the_spread": t["wall_min_s"] > p["wall_max_s"] or t["wall_max_s"] < p["wall_min_s"], "route_line_of_the_last_run": route}
+        if a.rocprof:
+            os.makedirs(a.rocprof, exist_ok=True)
+            res["rocprof"] = {}
+            for k in ("gzip6", "bgzf"):
+                cmd = legs[k + "/this"]
+                shutil.rmtree(cmd[-2], ignore_errors=True)
+                subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", a.rocprof, "-o", "longinflate_" + k, "--"] + cmd + ["--slow-exit"],
+                               stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=1700, check=True)
+                tot = kernel_totals(a.rocprof, "longinflate_" + k)
+                res["rocprof"][k] = {"kernels_ms": {n: v[0] for n, v in sorted(tot.items())}, "calls": {n: v[1] for n, v in sorted(tot.items())}}
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbases", type=float, default=2.0)
@@ -104,7 +205,10 @@ def main():
     ap.add_argument("--rocprof", default=None, help="directory: one more run of the long route and one of the FASTA stream under rocprofv3 --kernel-trace --stats")
     ap.add_argument("--tmp", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--gz", action="store_true", help="the compressed inputs of dist -A --long-inflate (DESIGN.md 4.20) against --parent-cli's --long-reads")
     a = ap.parse_args()
+    if a.gz:
+        return main_gz(a)
     from golden_cases import make_shuf
     tmp = tempfile.mkdtemp(prefix="bench_longreads_", dir=a.tmp)
     try:
