@@ -284,6 +284,18 @@ int mk_sketch_push_fastq_long(mk_engine *e, const uint8_t *text, uint64_t n, int
  * in HBM between pushes for both entries, so host and device pushes may alternate within one sketch.  After a failed push, or to
  * abandon a sketch whose last push was not final: mk_sketch_finish (result dropped), then mk_sketch_begin. */
 int mk_sketch_push_fastq_long_device(mk_engine *e, const uint8_t *d_text, uint64_t n, int final);
+/* The other FASTQ reader for text of any line length: fastq2co() (iseq2comem.c:343-379) with its fgets() width
+ * unbounded, into a sketch begun with mk_sketch_begin_occ.  Line roles, pieces, `final`, the open record in HBM, pinned and pageable
+ * text, the 2^31 limits and the sequence after a failed push are those of mk_sketch_push_fastq_long[_device]; the rule is
+ * mk_fastq_frame_q's: column i of a sequence line is written as 'N' when the signed byte at column i of the record's fourth line --
+ * its '\n' counted as its last byte, 0 behind that -- is below qmin (qmin <= -128 masks nothing); a record counts only when all four
+ * of its lines end in '\n' (text behind the last such record waits for the next push, or is dropped by the final one); the final
+ * push of a sketch that has counted no record walks the text's second line if there is one, masked by the fourth as far as that
+ * exists.  Wherever mk_fastq_frame_q accepts the text (lines below 19 999 characters) the sketch is the one its rows give.
+ * MK_MODE_OCC_SET sketches only, the same qmin in every push of a sketch, not mixed with mk_sketch_push_stream or the plain long
+ * pushes (MK_ERR_STATE each); host and device pushes may alternate. */
+int mk_sketch_push_fastq_long_q(mk_engine *e, const uint8_t *text, uint64_t n, int final, int32_t qmin);
+int mk_sketch_push_fastq_long_q_device(mk_engine *e, const uint8_t *d_text, uint64_t n, int final, int32_t qmin);
 /* device milliseconds of the framing kernels (mk_fql_*, the carry kernel included) of all mk_sketch_push_fastq_long[_device] calls
  * since mk_sketch_begin; waits for the last of them.  To be asked before the next mk_sketch_begin. */
 int mk_sketch_fastq_long_frame_ms(mk_engine *e, double *ms);
@@ -867,6 +879,9 @@ int mk_sketch_push_bgzf_q(mk_engine *e, int fd, size_t size, const mk_bgzf_opts 
  * MK_ERR_FORMAT with st->bad_block / st->bad_status, that chunk's text is not pushed; the sketch must be abandoned (mk_sketch_finish,
  * result dropped, then mk_sketch_begin). */
 int mk_sketch_push_bgzf_long(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int final, mk_bgzf_stats *st);
+/* The same into a sketch begun with mk_sketch_begin_occ by DESIGN.md 4.21's rule: every chunk's text goes to
+ * mk_sketch_push_fastq_long_q_device with qmin.  Statuses and `final` as above. */
+int mk_sketch_push_bgzf_long_q(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int32_t qmin, int final, mk_bgzf_stats *st);
 const char *mk_bgzf_last_error(void); /* text of the calling thread's last failed mk_sketch_push_bgzf / _q / _long, mk_sketch_push_gzip* */
 /* the stream the engine's kernels are queued on now and its device, for work that must be ordered with them (staged rows are
  * flushed first).  MK_ERR_STATE with MK_OPT_SPLIT_CUS (two queues: no single stream orders with the scan). */
@@ -1022,6 +1037,9 @@ int mk_sketch_push_gzip_q(mk_engine *e, int fd, size_t size, const mk_gunzip_opt
  * mk_fql_* and carry kernels.  MK_ERR_FORMAT with st->bad_status: as above the status may come after text was pushed, so the caller
  * finishes and drops the sketch, begins it anew and reads the file another way. */
 int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int final, mk_gunzip_stats *st);
+/* The same into a sketch begun with mk_sketch_begin_occ by DESIGN.md 4.21's rule: every batch's text goes to
+ * mk_sketch_push_fastq_long_q_device with qmin.  Statuses and `final` as above. */
+int mk_sketch_push_gzip_long_q(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int32_t qmin, int final, mk_gunzip_stats *st);
 
 /* ---- a BATCH of single-member gzip genome files, many wavefronts per file ----------------------------------------
  * mk_sketch_batch_begin_gz with the decode above in place of one wavefront per file: a wave per span of S compressed bytes finds

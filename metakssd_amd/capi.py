@@ -180,6 +180,8 @@ def _load():
         "mk_sketch_push_stream": [vp, vp, u64, C.c_int],
         "mk_sketch_push_fastq_long": [vp, vp, u64, C.c_int],
         "mk_sketch_push_fastq_long_device": [vp, vp, u64, C.c_int],
+        "mk_sketch_push_fastq_long_q": [vp, vp, u64, C.c_int, C.c_int32],
+        "mk_sketch_push_fastq_long_q_device": [vp, vp, u64, C.c_int, C.c_int32],
         "mk_sketch_fastq_long_frame_ms": [vp, C.POINTER(C.c_double)],
         "mk_partial_count_begin": [vp],
         "mk_partial_export_async": [vp, vp, vp, vp, u64, C.POINTER(u64)],
@@ -203,6 +205,7 @@ def _load():
         "mk_inflate_stream_members": [vp, C.POINTER(u64)],
         "mk_sketch_push_gzip": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), u64, C.POINTER(GunzipStatsC)],
         "mk_sketch_push_gzip_long": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), C.c_int, C.POINTER(GunzipStatsC)],
+        "mk_sketch_push_gzip_long_q": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), C.c_int32, C.c_int, C.POINTER(GunzipStatsC)],
         "mk_sketch_push_gzip_q": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), i32, u64, C.POINTER(GunzipStatsC)],
         "mk_inflate_members": [vp, vp, C.c_size_t, C.POINTER(GzMemberC), u32, vp, C.c_size_t, C.POINTER(GzMemberResultC)],
         "mk_sketch_finish": [vp, C.POINTER(ResultC)],
@@ -303,6 +306,7 @@ def _load():
         "mk_inflate_last_kernel_ms": [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)],
         "mk_sketch_push_bgzf": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), u64, C.POINTER(BgzfStatsC)],
         "mk_sketch_push_bgzf_long": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), C.c_int, C.POINTER(BgzfStatsC)],
+        "mk_sketch_push_bgzf_long_q": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), C.c_int32, C.c_int, C.POINTER(BgzfStatsC)],
         "mk_sketch_push_bgzf_q": [vp, C.c_int, C.c_size_t, C.POINTER(BgzfOptsC), i32, u64, C.POINTER(BgzfStatsC)],
     }
     for name, args in sig.items():
@@ -717,6 +721,59 @@ class Engine:
         fd = os.open(path, os.O_RDONLY)
         try:
             rc = lib.mk_sketch_push_bgzf_long(self.h, fd, os.fstat(fd).st_size, C.byref(o), 1 if final else 0, C.byref(st))
+        finally:
+            os.close(fd)
+        if rc:
+            err = MkError(rc, (lib.mk_bgzf_last_error() or b"").decode())
+            err.stats = st
+            raise err
+        return st
+
+    def push_fastq_long_q(self, text, qmin, final=True, piece=None):
+        """FASTQ text as it is in the file, lines of any length, into the begin(occ=...) sketch in progress by fastq2co's rule: bases
+        whose quality byte is below qmin masked (mk_sketch_push_fastq_long_q); piece: push in pieces of that many bytes (the last
+        one final)"""
+        b = np.frombuffer(bytes(text), dtype=np.uint8)
+        if not piece:
+            _check(lib.mk_sketch_push_fastq_long_q(self.h, b.ctypes.data if len(b) else None, len(b), 1 if final else 0, qmin), self.h)
+            return
+        at = 0
+        while True:
+            n = min(piece, len(b) - at)
+            last = at + n >= len(b)
+            part = np.ascontiguousarray(b[at:at + n])
+            _check(lib.mk_sketch_push_fastq_long_q(self.h, part.ctypes.data if n else None, n, 1 if (last and final) else 0, qmin), self.h)
+            at += n
+            if last:
+                break
+
+    def push_fastq_long_q_device(self, dev_ptr, n, qmin, final=True):
+        """n bytes of FASTQ text at dev_ptr, in the memory of the engine's device, any alignment -> mk_sketch_push_fastq_long_q_device;
+        returns with the work queued: the memory stays untouched until the next call on this engine that waits"""
+        _check(lib.mk_sketch_push_fastq_long_q_device(self.h, C.c_void_p(dev_ptr) if n else None, n, 1 if final else 0, qmin), self.h)
+
+    def push_gzip_long_q(self, path, qmin, span_bytes=0, ratio=0, batch_spans=0, members=False, final=True):
+        """push_gzip_long for the MK_MODE_OCC_SET sketch in progress, bases below qmin masked (mk_sketch_push_gzip_long_q) ->
+        GunzipStatsC; statuses as push_gzip_long"""
+        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), GunzipStatsC()
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            rc = lib.mk_sketch_push_gzip_long_q(self.h, fd, os.fstat(fd).st_size, C.byref(o), qmin, 1 if final else 0, C.byref(st))
+        finally:
+            os.close(fd)
+        if rc:
+            err = MkError(rc, (lib.mk_bgzf_last_error() or b"").decode())
+            err.stats = st
+            raise err
+        return st
+
+    def push_bgzf_long_q(self, path, qmin, chunk_bytes=0, final=True):
+        """push_bgzf_long for the MK_MODE_OCC_SET sketch in progress, bases below qmin masked (mk_sketch_push_bgzf_long_q) ->
+        BgzfStatsC; statuses as push_bgzf_long"""
+        o, st = BgzfOptsC(chunk_bytes, 0), BgzfStatsC()
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            rc = lib.mk_sketch_push_bgzf_long_q(self.h, fd, os.fstat(fd).st_size, C.byref(o), qmin, 1 if final else 0, C.byref(st))
         finally:
             os.close(fd)
         if rc:

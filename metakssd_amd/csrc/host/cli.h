@@ -107,6 +107,11 @@ typedef struct {
                             * to the long-read framing -- a BGZF chain by mk_sketch_push_bgzf_long, another single gzip stream by
                             * mk_sketch_push_gzip_long; everything else reads as under --long-reads.  A switch of its own because
                             * --long-reads refuses --device-inflate and --device-gunzip, which name the short-read framing */
+  int long_reads_q;        /* --long-reads-q: the same for the other FASTQ reader, dist without -A (-n, -Q): fastq2co's record rule and quality
+                            * mask on lines of any length (mk_sketch_push_fastq_long_q).  Opt-in: without the switch a line of
+                            * 19 999+ characters is refused as before */
+  int long_inflate_q;      /* --long-inflate-q (implies --long-reads-q): its .gz inputs inflated on the device, by mk_sketch_push_bgzf_long_q /
+                            * mk_sketch_push_gzip_long_q */
   int device_inflate_given; /* --device-inflate was on the command line (what --long-reads refuses) */
   mk_gunzip_opts gunzip_opts;   /* --gunzip-span-bytes, --gunzip-ratio, --gunzip-batch-spans (test hooks; 0 = the library's defaults) */
   uint64_t inflate_chunk_bytes; /* --inflate-chunk-kib: text bytes per chunk of the device route (test hook; 0 = the library's default) */

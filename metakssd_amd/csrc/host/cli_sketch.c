@@ -606,12 +606,17 @@ static size_t long_read_plain(int fd, uint8_t *dst, off_t off, size_t want, int 
   }
   return have;
 }
-static void report_long(const char *path, unsigned long long pieces, unsigned long long bytes, double t_in) {
+static void report_long(const char *path, const char *route, unsigned long long pieces, unsigned long long bytes, double t_in) {
   if (!g_opt.timing) return;
   char fb[160] = "";
   if (g_gz_fallback) snprintf(fb, sizeof fb, ", \"fallback\": \"%s\"", g_gz_fallback);
-  printf("{\"input\": \"%s\", \"route\": \"long-reads\", \"source\": \"%s\", \"pieces\": %llu, \"text_bytes\": %llu, \"route_total_s\": %.4f%s}\n", path,
-         is_compressed(path) ? "zcat" : "file", pieces, bytes, now_s() - t_in, fb);
+  printf("{\"input\": \"%s\", \"route\": \"%s\", \"source\": \"%s\", \"pieces\": %llu, \"text_bytes\": %llu, \"route_total_s\": %.4f%s}\n", path,
+         route, is_compressed(path) ? "zcat" : "file", pieces, bytes, now_s() - t_in, fb);
+}
+/* the long route of this file's reader: -A or -n / -Q (c->occ: fastq2co's rule with the -Q mask, 4.21) */
+static const char *long_route(const ctx_t *c) { return c->occ ? "long-reads-q" : "long-reads"; }
+static int long_push(const ctx_t *c, mk_engine *e, const uint8_t *text, uint64_t n, int final) {
+  return c->occ ? mk_sketch_push_fastq_long_q(e, text, n, final, c->qmin) : mk_sketch_push_fastq_long(e, text, n, final);
 }
 static void sketch_fastq_long(ctx_t *c, const char *path) {
   for (int k = 0; k < 2; k++)
@@ -630,17 +635,17 @@ static void sketch_fastq_long(ctx_t *c, const char *path) {
     if (plain) have = long_read_plain(fileno(in.f), c->long_buf[k], (off_t)bytes, LONG_CHUNK, c->nthreads);
     else while (have < LONG_CHUNK && (r = fread(c->long_buf[k] + have, 1, LONG_CHUNK - have, in.f)) > 0) have += r;
     if (have == 0) break;
-    CHECK(e, mk_sketch_push_fastq_long(e, c->long_buf[k], have, 0));
+    CHECK(e, long_push(c, e, c->long_buf[k], have, 0));
     pieces++; bytes += have;
     if (have < LONG_CHUNK) break;
   }
-  CHECK(e, mk_sketch_push_fastq_long(e, NULL, 0, 1));
+  CHECK(e, long_push(c, e, NULL, 0, 1));
   /* --long-inflate: the device route had the file first and gave it up with a status.  The line then comes in front of the wait for
    * zcat, which may call the file damaged and end the run: why the file came this way is said either way */
-  if (g_gz_fallback) report_long(path, pieces, bytes, t_in);
+  if (g_gz_fallback) report_long(path, long_route(c), pieces, bytes, t_in);
   close_input(&in);
   c->t_last_push = now_s() - g_t0;
-  if (!g_gz_fallback) report_long(path, pieces, bytes, t_in);
+  if (!g_gz_fallback) report_long(path, long_route(c), pieces, bytes, t_in);
 }
 /* --long-inflate: a .gz of the long-read route is inflated on the device and its text goes from HBM to the same framing.
  * A BGZF chain takes mk_sketch_push_bgzf_long, another file that mk_gzip_scan_stream calls single takes mk_sketch_push_gzip_long; 0:
@@ -648,7 +653,7 @@ static void sketch_fastq_long(ctx_t *c, const char *path) {
  * file from its start through sketch_fastq_long (`zcat -fc`), which alone decides whether it is damaged.  A damaged BGZF block ends
  * the run with sketch_fastq_bgzf's message.  One file is one sketch here, so every call closes the stream (final). */
 static int sketch_fastq_long_inflate(ctx_t *c, const char *path) {
-  if (!g_opt.long_inflate || !c->bgzf_ok || g_opt.no_device_inflate || !has_suffix(path, ".gz")) return 0;
+  if (!(c->occ ? g_opt.long_inflate_q : g_opt.long_inflate) || !c->bgzf_ok || g_opt.no_device_inflate || !has_suffix(path, ".gz")) return 0;
   const int fd = open(path, O_RDONLY);
   if (fd < 0) return 0;
   struct stat st;
@@ -665,16 +670,16 @@ static int sketch_fastq_long_inflate(ctx_t *c, const char *path) {
     memset(&o, 0, sizeof o);
     o.chunk_bytes = g_opt.inflate_chunk_bytes;
     mk_bgzf_stats bs;
-    const int rc = mk_sketch_push_bgzf_long(e, fd, (size_t)st.st_size, &o, 1, &bs);
+    const int rc = c->occ ? mk_sketch_push_bgzf_long_q(e, fd, (size_t)st.st_size, &o, c->qmin, 1, &bs) : mk_sketch_push_bgzf_long(e, fd, (size_t)st.st_size, &o, 1, &bs);
     close(fd);
     if (rc == MK_ERR_FORMAT && bs.bad_block >= 0)
       die("%s: BGZF block %lld is damaged (%s): the input was not read completely", path, (long long)bs.bad_block, mk_inflate_status_text(bs.bad_status));
-    if (rc != MK_OK) die("mk_sketch_push_bgzf_long failed (%d): %s", rc, mk_bgzf_last_error());
+    if (rc != MK_OK) die("%s failed (%d): %s", c->occ ? "mk_sketch_push_bgzf_long_q" : "mk_sketch_push_bgzf_long", rc, mk_bgzf_last_error());
     c->t_last_push = now_s() - g_t0;
     if (g_opt.timing)
-      printf("{\"input\": \"%s\", \"route\": \"long-reads\", \"source\": \"device-inflate\", \"blocks\": %llu, \"chunks\": %llu, \"comp_bytes\": %llu, "
+      printf("{\"input\": \"%s\", \"route\": \"%s\", \"source\": \"device-inflate\", \"blocks\": %llu, \"chunks\": %llu, \"comp_bytes\": %llu, "
              "\"text_bytes\": %llu, \"inflate_ms\": %.3f, \"frame_ms\": %.3f, \"bgzf_scan_s\": %.4f, \"read_s\": %.4f, \"route_total_s\": %.4f}\n",
-             path, (unsigned long long)bs.blocks, (unsigned long long)bs.chunks, (unsigned long long)bs.comp_bytes, (unsigned long long)bs.text_bytes,
+             path, long_route(c), (unsigned long long)bs.blocks, (unsigned long long)bs.chunks, (unsigned long long)bs.comp_bytes, (unsigned long long)bs.text_bytes,
              bs.inflate_ms, bs.frame_ms, bs.t_scan_s, bs.t_read_s, now_s() - t_in);
     return 1;
   }
@@ -683,26 +688,27 @@ static int sketch_fastq_long_inflate(ctx_t *c, const char *path) {
   mk_engine *e = sketch_engine(c);
   if (c->t_first_push == 0) c->t_first_push = now_s() - g_t0;
   mk_gunzip_stats gs;
-  const int rc = mk_sketch_push_gzip_long(e, fd, (size_t)st.st_size, &g_opt.gunzip_opts, 1, &gs);
+  const int rc = c->occ ? mk_sketch_push_gzip_long_q(e, fd, (size_t)st.st_size, &g_opt.gunzip_opts, c->qmin, 1, &gs)
+                        : mk_sketch_push_gzip_long(e, fd, (size_t)st.st_size, &g_opt.gunzip_opts, 1, &gs);
   close(fd);
   if (rc == MK_ERR_FORMAT && gs.bad_status) {
     drop_pushed_and_fall_back(c, e, mk_gunzip_status_text(gs.bad_status));
     return 0;
   }
-  if (rc != MK_OK) die("mk_sketch_push_gzip_long failed (%d): %s", rc, mk_bgzf_last_error());
+  if (rc != MK_OK) die("%s failed (%d): %s", c->occ ? "mk_sketch_push_gzip_long_q" : "mk_sketch_push_gzip_long", rc, mk_bgzf_last_error());
   c->t_last_push = now_s() - g_t0;
   if (g_opt.timing) {
     char members[48] = ""; /* --gunzip-members: how many the file had */
     if (g_opt.gunzip_opts.flags & MK_GUNZIP_MEMBERS) snprintf(members, sizeof members, ", \"members\": %u", gs.members);
-    printf("{\"input\": \"%s\", \"route\": \"long-reads\", \"source\": \"device-gunzip\", \"pieces\": %llu, \"batches\": %llu, \"comp_bytes\": %llu, "
+    printf("{\"input\": \"%s\", \"route\": \"%s\", \"source\": \"device-gunzip\", \"pieces\": %llu, \"batches\": %llu, \"comp_bytes\": %llu, "
            "\"text_bytes\": %llu, \"find_ms\": %.3f, \"decode_ms\": %.3f, \"resolve_ms\": %.3f, \"frame_ms\": %.3f, \"read_s\": %.4f, \"route_total_s\": %.4f%s}\n",
-           path, (unsigned long long)gs.pieces, (unsigned long long)gs.batches, (unsigned long long)gs.comp_bytes, (unsigned long long)gs.text_bytes,
+           path, long_route(c), (unsigned long long)gs.pieces, (unsigned long long)gs.batches, (unsigned long long)gs.comp_bytes, (unsigned long long)gs.text_bytes,
            gs.find_ms, gs.decode_ms, gs.resolve_ms, gs.frame_ms, gs.t_read_s, now_s() - t_in, members);
   }
   return 1;
 }
 static void sketch_fastq(ctx_t *c, const char *path) {
-  if (g_opt.long_reads && !c->occ) {
+  if (c->occ ? g_opt.long_reads_q : g_opt.long_reads) {
     if (!sketch_fastq_long_inflate(c, path)) sketch_fastq_long(c, path);
     g_gz_fallback = NULL;
     return;
@@ -1801,7 +1807,7 @@ int run_stage1(int stage2_after) {
    * engines beside a working one takes 0.04 to 1 s each, two pay, more do not.  --engines 1 turns it off */
   if (o->engines_per_gpu < 0 || o->engines_per_gpu > MAX_ENGINES_PER_GPU) die("--engines takes 1..%d", MAX_ENGINES_PER_GPU);
   plan_batches(s, &B);
-  const int n_engines = s->n_engines = (!s->use_batch && !shard_files && ndev <= 1 && files->n >= 8 && !fu->on && !o->long_reads) ? (o->engines_per_gpu ? o->engines_per_gpu : MK_DEFAULT_ENGINES) : 1;
+  const int n_engines = s->n_engines = (!s->use_batch && !shard_files && ndev <= 1 && files->n >= 8 && !fu->on && !o->long_reads && !o->long_reads_q) ? (o->engines_per_gpu ? o->engines_per_gpu : MK_DEFAULT_ENGINES) : 1;
   if (n_engines > 1) {
     s->extra.P = P; s->extra.device = ndev ? o->devs[0] : device; s->extra.want = n_engines - 1;
     if (pthread_create(&s->extra.th, NULL, extra_engines_run, &s->extra) != 0) die("cannot start a thread: %s", strerror(errno));
@@ -1826,7 +1832,7 @@ int run_stage1(int stage2_after) {
   int rc = fu->on ? MK_OK : mk_sketchdir_open(o->outdir, P, koc_dir, files->n, &s->sd);
   if (rc != MK_OK) die("cannot create sketch directory %s (%d)", o->outdir, rc);
   s->jo = (job_opts){files, P, o->abundance, o->uniq, first_nonfq, o->kmerocrs, o->kmerqlty, s->nthreads, s->quiet, &s->pf, 0};
-  if (files->n > 1 && s->nthreads > 1 && !s->use_batch && !o->long_reads) start_prefetch(s, first_nonfq); /* (its workers frame FASTQ files into rows) */
+  if (files->n > 1 && s->nthreads > 1 && !s->use_batch && !o->long_reads && !o->long_reads_q) start_prefetch(s, first_nonfq); /* (its workers frame FASTQ files into rows) */
   if (first_nonfq < files->n && o->abundance) printf("Warning: close abundance mode (-A) since non-fastq file input.\n");
   if (s->use_batch) run_batches(s, &B);
   else if (shard_files) run_sharded(s);

@@ -105,6 +105,8 @@ static void parse_dist_options(int argc, char **argv) {
     else if (!strcmp(argv[i], "--device-inflate")) { o->no_device_inflate = 0; o->gz_batches = 1; o->device_inflate_q = 1; o->device_inflate_given = 1; }
     else if (!strcmp(argv[i], "--long-reads")) o->long_reads = 1; /* dist -A: FASTQ lines of any length through the base stream */
     else if (!strcmp(argv[i], "--long-inflate")) o->long_reads = o->long_inflate = 1; /* ... and a .gz inflated on the device in front of it */
+    else if (!strcmp(argv[i], "--long-reads-q")) o->long_reads_q = 1; /* dist -n / -Q: the same for fastq2co's reader, quality mask on the device */
+    else if (!strcmp(argv[i], "--long-inflate-q")) o->long_reads_q = o->long_inflate_q = 1;
     else if (!strcmp(argv[i], "--device-gunzip")) o->device_gunzip = 1; /* dist -A and dist -n / -Q: a single-member .gz FASTQ inflated on the device */
     else if (!strcmp(argv[i], "--gunzip-members")) o->gunzip_opts.flags |= MK_GUNZIP_MEMBERS; /* ... and a concatenation of members */
     else if (!strcmp(argv[i], "--gunzip-span-bytes") && more) o->gunzip_opts.span_bytes = (uint32_t)atoll(argv[++i]);
@@ -140,6 +142,15 @@ static int dist_dispatch(void) {
   cli_opts *o = &g_opt;
   strlist *args = &o->args;
   int stage2_after = 0;
+  if (o->long_reads_q) { /* the long route of the -n / -Q reader: what it cannot do is said before the device is touched */
+    const char *sw = o->long_inflate_q ? "--long-inflate-q" : "--long-reads-q";
+    if (o->long_reads) die("%s is the route of dist without -A: not with %s", sw, o->long_inflate ? "--long-inflate" : "--long-reads");
+    if (o->abundance) die("%s does not go with -A: --long-reads is the route of the counted sketch", sw);
+    if (o->ndev) die("%s works on one GPU: --device D, not --devices", sw);
+    if (o->composite_db) die("%s does not go with --composite: the report reads the counted sketch", sw);
+    if ((o->device_inflate_given || o->device_gunzip) && o->long_inflate_q) die("--long-inflate-q chooses the device route itself: not --device-inflate or --device-gunzip");
+    if (o->device_inflate_given || o->device_gunzip) die("--long-reads-q reads .gz files through zcat: not --device-inflate or --device-gunzip");
+  }
   if (o->long_reads) { /* the long-read route: what it cannot do is said before the device is touched */
     const char *sw = o->long_inflate ? "--long-inflate" : "--long-reads";
     if (!o->abundance) die("%s needs -A: it is the route of the counted sketch", sw);
@@ -201,6 +212,10 @@ int main(int argc, char **argv) {
         if (!strcmp(argv[j], "--long-inflate")) die("--long-inflate does not go with --byread: per-read sketches keep the framing contract");
       for (int j = 2; j < argc; j++)
         if (!strcmp(argv[j], "--long-reads")) die("--long-reads does not go with --byread: per-read sketches keep the framing contract");
+      for (int j = 2; j < argc; j++)
+        if (!strcmp(argv[j], "--long-inflate-q")) die("--long-inflate-q does not go with --byread: per-read sketches keep the framing contract");
+      for (int j = 2; j < argc; j++)
+        if (!strcmp(argv[j], "--long-reads-q")) die("--long-reads-q does not go with --byread: per-read sketches keep the framing contract");
       return cmd_dist_byread(argc - 2, argv + 2);
     }
   parse_dist_options(argc - 2, argv + 2);

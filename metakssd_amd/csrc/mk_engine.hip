@@ -150,6 +150,12 @@ struct mk_engine {
   bool fq_timed = false;
   double fq_frame_ms = 0;
   bool fq_used = false, fq_pending = false; /* fq_pending: a non-final push is queued, its state has not been read back */
+  /* mk_sketch_push_fastq_long_q: the last three newlines in front of every segment, one entry more for the whole text */
+  mk_fqq_nl *d_fq_last = nullptr;
+  size_t fq_last_cap = 0;
+  bool fq_q = false;      /* this sketch's long pushes are the quality-aware ones (chosen by the first) */
+  int32_t fq_qmin = 0;    /* their -Q, the same in every push */
+  bool fq_counted = false; /* a settled push of this sketch has given a record (decides the first-record exception) */
 
   /* batches of small inputs (mk_sketch_batch_begin / _end): three contexts, two batches in flight, the third holds the results
    * handed out last */
@@ -339,7 +345,7 @@ extern "C" int mk_engine_destroy(mk_engine *e) {
   if (e->ev_scan_post) hipEventDestroy(e->ev_scan_post);
   if (e->ev_res) hipEventDestroy(e->ev_res);
   hipFree(e->d_text); hipFree(e->d_stream); hipFree(e->d_stream_tmp); hipFree(e->d_fa_sum); hipFree(e->d_fa_state);
-  hipFree(e->d_fq_sum); hipFree(e->d_fq_carry);
+  hipFree(e->d_fq_sum); hipFree(e->d_fq_carry); hipFree(e->d_fq_last);
   for (hipEvent_t ev : e->ev_fq) if (ev) hipEventDestroy(ev);
   if (e->h_fa_state) hipHostFree(e->h_fa_state);
   for (int i = 0; i < MK_TICKETS; i++) if (e->ev_ticket[i]) hipEventDestroy(e->ev_ticket[i]);
@@ -685,6 +691,7 @@ static int mk_poison_scratch(mk_engine *e) {
   if (e->d_stream_tmp) MK_HIP(e, mk_dev_repoison(e->d_stream_tmp, 8192, s));
   if (e->d_fa_sum) MK_HIP(e, mk_dev_repoison(e->d_fa_sum, e->fa_sum_cap * sizeof(mk_fa_sum), s));
   if (e->d_fq_sum) MK_HIP(e, mk_dev_repoison(e->d_fq_sum, e->fq_sum_cap * sizeof(mk_fql_sum), s));
+  if (e->d_fq_last) MK_HIP(e, mk_dev_repoison(e->d_fq_last, e->fq_last_cap * sizeof(mk_fqq_nl), s));
   if (e->d_fq_carry) MK_HIP(e, mk_dev_repoison(e->d_fq_carry, e->fq_carry_cap, s)); /* (an open record of a sketch that was never closed is dropped by the begin) */
   if (e->d_stage[0] && e->copy_stream == e->stream) /* (rows staged for a sketch that was never finished are dropped by the begin) */
     for (int i = 0; i < MK_REGIONS; i++) MK_HIP(e, mk_dev_repoison(e->d_stage[i], e->stage_bytes, s));
@@ -1000,6 +1007,7 @@ extern "C" int mk_sketch_begin(mk_engine *e, int mode) {
   e->D = 0;
   e->fa_used = false; e->fa_final = false; e->fa_tail = 0; e->fa_rows_done = 0; e->fa_pitch = 0;
   e->fq_used = false; e->fq_pending = false; e->fq_carry_len = 0; e->fq_total = 0; e->fq_timed = false; e->fq_frame_ms = 0;
+  e->fq_q = false; e->fq_qmin = 0; e->fq_counted = false;
   return MK_OK;
 }
 
@@ -1519,6 +1527,7 @@ static int mk_fql_settle(mk_engine *e) {
   /* d_text held the old carry and the piece: what lies behind the last record end is the new carry (no record end: all of it), and
    * mk_fql_carry_kernel has moved it to d_fq_carry */
   e->fq_carry_len = total - consumed;
+  if (consumed) e->fq_counted = true;
   return mk_fql_frame_time(e);
 }
 
@@ -1545,6 +1554,14 @@ static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int 
     MK_HIP(e, mk_dev_alloc(&e->d_fq_sum, (nseg + nseg / 4 + 256) * sizeof(mk_fql_sum)));
     e->fq_sum_cap = nseg + nseg / 4 + 256;
   }
+  const bool q = e->fq_q;
+  if (q && nseg + 1 > e->fq_last_cap) { /* (one entry a segment and one for the whole text: sized from the text's length alone) */
+    MK_HIP(e, hipStreamSynchronize(e->stream));
+    hipFree(e->d_fq_last);
+    e->d_fq_last = nullptr; e->fq_last_cap = 0;
+    MK_HIP(e, mk_dev_alloc(&e->d_fq_last, (nseg + nseg / 4 + 256) * sizeof(mk_fqq_nl)));
+    e->fq_last_cap = nseg + nseg / 4 + 256;
+  }
   if (!e->fa_pitch) e->fa_pitch = (final && total <= MK_FA_SMALL_BYTES) ? MK_FA_PITCH_SMALL : MK_FA_PITCH; /* a whole small text at once */
   const uint32_t TL = (uint32_t)e->P.TL, pitch = e->fa_pitch, rowlen = pitch + TL - 1u;
   const uint32_t width = (rowlen + 1u + 15u) & ~15u;
@@ -1558,11 +1575,26 @@ static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int 
   if (n) MK_HIP(e, hipMemcpyAsync(e->d_text + c, text, (size_t)n, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
   if (!pinned) MK_HIP(e, hipStreamSynchronize(e->stream)); /* pageable memory: free again when the call returns */
   MK_HIP(e, hipEventRecord(e->ev_fq[0], e->stream));
-  if (nseg) hipLaunchKernelGGL(mk_fql_summary_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text, total, e->d_fq_sum);
-  hipLaunchKernelGGL(mk_fql_scan_kernel, dim3(1), dim3(1024), 0, e->stream, e->d_fq_sum, nseg, (const uint8_t *)e->d_text, total, e->d_fa_state,
-                     e->d_stream, pitch, rowlen, TL, final ? 1 : 0);
-  if (nseg) hipLaunchKernelGGL(mk_fql_emit_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text,
-                               (const mk_fql_sum *)e->d_fq_sum, (const mk_fa_state *)e->d_fa_state, e->d_stream, (unsigned long long)e->fa_tail);
+  if (q) { /* fastq2co's rule: the stream is written from the quality lines (mk_fastq_long.hip.h) */
+    const dim3 segs((unsigned)((nseg + 3) / 4));
+    if (nseg) hipLaunchKernelGGL(mk_fqq_summary_kernel, segs, dim3(256), 0, e->stream, (const uint8_t *)e->d_text, total, e->d_fq_sum, e->d_fq_last);
+    hipLaunchKernelGGL(mk_fqq_scan_kernel, dim3(1), dim3(1024), 0, e->stream, e->d_fq_sum, nseg, (const uint8_t *)e->d_text, total, e->d_fa_state,
+                       e->d_stream, pitch, rowlen, TL, final ? 1 : 0, e->d_fq_last);
+    if (nseg) hipLaunchKernelGGL(mk_fqq_emit_kernel, segs, dim3(256), 0, e->stream, (const uint8_t *)e->d_text, (const mk_fql_sum *)e->d_fq_sum,
+                                 (const mk_fqq_nl *)e->d_fq_last, (const mk_fa_state *)e->d_fa_state, e->d_stream, (unsigned long long)e->fa_tail,
+                                 e->fq_qmin);
+    /* the first record of a file is walked whenever its second line exists: only where no push has given a record, this one included
+     * (the kernel looks at this push's `consumed` itself) */
+    if (final && nseg && !e->fq_counted)
+      hipLaunchKernelGGL(mk_fqq_first_kernel, dim3((unsigned)(nseg < 1024u ? (nseg + 3) / 4 : 256u)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text, total, (const mk_fqq_nl *)(e->d_fq_last + nseg),
+                         e->d_fa_state, e->d_stream, (unsigned long long)e->fa_tail, pitch, TL, e->fq_qmin);
+  } else {
+    if (nseg) hipLaunchKernelGGL(mk_fql_summary_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text, total, e->d_fq_sum);
+    hipLaunchKernelGGL(mk_fql_scan_kernel, dim3(1), dim3(1024), 0, e->stream, e->d_fq_sum, nseg, (const uint8_t *)e->d_text, total, e->d_fa_state,
+                       e->d_stream, pitch, rowlen, TL, final ? 1 : 0);
+    if (nseg) hipLaunchKernelGGL(mk_fql_emit_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, e->stream, (const uint8_t *)e->d_text,
+                                 (const mk_fql_sum *)e->d_fq_sum, (const mk_fa_state *)e->d_fa_state, e->d_stream, (unsigned long long)e->fa_tail);
+  }
   /* the open record leaves d_text before the next push rewrites it -- and before that push's scan kernel rewrites st->in_header */
   if (!final && nseg) hipLaunchKernelGGL(mk_fql_carry_kernel, dim3(256), dim3(256), 0, e->stream, (const uint8_t *)e->d_text, total,
                                          (const mk_fa_state *)e->d_fa_state, e->d_fq_carry);
@@ -1588,12 +1620,17 @@ static int mk_fql_push_piece(mk_engine *e, const uint8_t *text, uint64_t n, int 
   return pinned ? MK_OK : mk_fql_settle(e);
 }
 
-static int mk_fql_push(mk_engine *e, const char *who, const uint8_t *text, uint64_t n, int final, bool from_device) {
+/* q: fastq2co's rule with the -Q mask qmin (MK_MODE_OCC_SET); otherwise mt_shortreads2koc's (MK_MODE_KOC) */
+static int mk_fql_push(mk_engine *e, const char *who, const uint8_t *text, uint64_t n, int final, bool from_device, bool q = false, int32_t qmin = 0) {
   if (!e || (!text && n)) return MK_ERR_ARG;
   if (!e->begun) return mk_fail(e, MK_ERR_STATE, "push before mk_sketch_begin");
-  if (e->mode != MK_MODE_KOC) return mk_fail(e, MK_ERR_STATE, "%s: for MK_MODE_KOC sketches only", who);
+  if (!q && e->mode != MK_MODE_KOC) return mk_fail(e, MK_ERR_STATE, "%s: for MK_MODE_KOC sketches only", who);
+  if (q && e->mode != MK_MODE_OCC_SET) return mk_fail(e, MK_ERR_STATE, "%s: for MK_MODE_OCC_SET sketches only", who);
+  /* (the two rules cannot meet in one sketch: each wants another mode, and the mode is fixed at the begin) */
   if (e->fa_final) return mk_fail(e, MK_ERR_STATE, "%s: the stream has been closed (final) for this sketch", who);
   if (e->fa_used && !e->fq_used) return mk_fail(e, MK_ERR_STATE, "%s: this sketch has taken FASTA text (mk_sketch_push_stream)", who);
+  if (e->fq_used && q && e->fq_qmin != qmin)
+    return mk_fail(e, MK_ERR_STATE, "%s: qmin %d, but this sketch's pushes so far had %d", who, (int)qmin, (int)e->fq_qmin);
   if (n >= (1ull << 31)) return mk_fail(e, MK_ERR_ARG, "%s: at most 2^31 - 1 bytes per call", who);
   if (e->P.TL + MK_FA_PITCH > 4000u) return mk_fail(e, MK_ERR_ARG, "%s: k-mer too long for the stream rows", who);
   MK_HIP(e, hipSetDevice(e->device));
@@ -1605,6 +1642,7 @@ static int mk_fql_push(mk_engine *e, const char *who, const uint8_t *text, uint6
     }
   }
   { int rc = mk_flush_region(e); if (rc) return rc; }
+  e->fq_q = q; e->fq_qmin = qmin;
   for (;;) {
     int rc = mk_fql_settle(e);
     if (rc) return rc;
@@ -1625,6 +1663,15 @@ extern "C" int mk_sketch_push_fastq_long(mk_engine *e, const uint8_t *text, uint
  * caller's buffer is free once work queued later on that stream may overwrite it; returns with its work queued */
 extern "C" int mk_sketch_push_fastq_long_device(mk_engine *e, const uint8_t *d_text, uint64_t n, int final) {
   return mk_fql_push(e, "mk_sketch_push_fastq_long_device", d_text, n, final, true);
+}
+
+/* fastq2co's reader for text of any line length: the same pushes with the quality-aware kernels */
+extern "C" int mk_sketch_push_fastq_long_q(mk_engine *e, const uint8_t *text, uint64_t n, int final, int32_t qmin) {
+  return mk_fql_push(e, "mk_sketch_push_fastq_long_q", text, n, final, false, true, qmin);
+}
+
+extern "C" int mk_sketch_push_fastq_long_q_device(mk_engine *e, const uint8_t *d_text, uint64_t n, int final, int32_t qmin) {
+  return mk_fql_push(e, "mk_sketch_push_fastq_long_q_device", d_text, n, final, true, true, qmin);
 }
 
 extern "C" int mk_sketch_fastq_long_frame_ms(mk_engine *e, double *ms) {

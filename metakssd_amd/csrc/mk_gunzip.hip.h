@@ -918,8 +918,11 @@ static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts 
 /* The long sink: the same stream decode, every batch's text to mk_sketch_push_fastq_long_device.  The engine copies
  * the text into its own buffer on R.S, which is its stream, so R.d_text is free for the next batch's resolve; the open record waits
  * in the engine.  No framer, no carry of this route's, no slices: a batch holds less than 2^31 bytes of text. */
-extern "C" int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int final, mk_gunzip_stats *st) {
+static int mk_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int final, mk_gunzip_stats *st, bool q, int32_t qmin) {
   if (!e || fd < 0) return MK_ERR_ARG;
+  auto long_push = [&](const uint8_t *d, uint64_t n, int fin) -> int { /* q: fastq2co's rule with its mask */
+    return q ? mk_sketch_push_fastq_long_q_device(e, d, n, fin, qmin) : mk_sketch_push_fastq_long_device(e, d, n, fin);
+  };
   mk_gunzip_stats stats;
   memset(&stats, 0, sizeof stats);
   stats.bad_piece = -1;
@@ -950,7 +953,7 @@ extern "C" int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const
   auto sink = [&](uint8_t *d_text, uint64_t n, bool final_batch) -> int {
     const int fin = final && final_batch;
     if (n == 0 && !fin) return MK_OK;
-    const int prc = mk_sketch_push_fastq_long_device(e, d_text + MK_FQ_CARRY, n, fin);
+    const int prc = long_push(d_text + MK_FQ_CARRY, n, fin);
     if (prc) snprintf(R.err, sizeof R.err, "%s", mk_last_error(e));
     else if (fin) closed = true;
     return prc;
@@ -958,7 +961,7 @@ extern "C" int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const
   mk_gun_result res;
   rc = mk_gun_stream(R, size, info, opts, read, sink, nullptr, res);
   if (!rc && !res.status && final && !closed) { /* (no batch called itself the last one: the stream had no piece to give) */
-    rc = mk_sketch_push_fastq_long_device(e, nullptr, 0, 1);
+    rc = long_push(nullptr, 0, 1);
     if (rc) snprintf(R.err, sizeof R.err, "%s", mk_last_error(e));
   }
   (void)hipStreamSynchronize(R.S);
@@ -976,6 +979,14 @@ extern "C" int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const
     return MK_ERR_FORMAT;
   }
   return MK_OK;
+}
+
+extern "C" int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int final, mk_gunzip_stats *st) {
+  return mk_push_gzip_long(e, fd, size, opts, final, st, false, 0);
+}
+
+extern "C" int mk_sketch_push_gzip_long_q(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int32_t qmin, int final, mk_gunzip_stats *st) {
+  return mk_push_gzip_long(e, fd, size, opts, final, st, true, qmin);
 }
 
 extern "C" int mk_sketch_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, uint64_t first_ordinal, mk_gunzip_stats *st) {

@@ -786,7 +786,8 @@ static thread_local char mk_bgzf_err[256];
 
 /* both readers' route: occ == false is mk_fastq_frame's rule (-A), occ == true mk_fastq_frame_q's (quality mask qmin).  lng: the long
  * sink -- scan, chunks, upload and inflate are the same; a chunk's text goes to mk_sketch_push_fastq_long_device
- * instead of the framer, `final` with the file's last chunk when final_in says the sketch ends with this file. */
+ * instead of the framer (occ: to mk_sketch_push_fastq_long_q_device with qmin, 4.21), `final` with the file's last chunk when final_in
+ * says the sketch ends with this file. */
 static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, bool occ, int32_t qmin, uint64_t first_ordinal, mk_bgzf_stats *st,
                         bool lng = false, int final_in = 1) {
   if (!e || fd < 0) return MK_ERR_ARG;
@@ -877,8 +878,12 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
     return MK_OK;
   };
 
+  /* the long sink's push: occ chooses fastq2co's rule with its mask */
+  auto long_push = [&](const uint8_t *d, uint64_t n, int fin) -> int {
+    return occ ? mk_sketch_push_fastq_long_q_device(e, d, n, fin, qmin) : mk_sketch_push_fastq_long_device(e, d, n, fin);
+  };
   if (lng && chunks.empty()) { /* (a file without a member has no text) */
-    if (final_in && (rc = mk_sketch_push_fastq_long_device(e, nullptr, 0, 1))) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
+    if (final_in && (rc = long_push(nullptr, 0, 1))) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
     stats.comp_bytes = size; stats.t_total_s = mk_now_s() - t_begin;
     if (st) *st = stats;
     return MK_OK;
@@ -914,7 +919,7 @@ static int mk_push_bgzf(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o
         result = MK_ERR_FORMAT;
         break;
       }
-      rc = mk_sketch_push_fastq_long_device(e, R.d_text[s] + MK_FQ_CARRY, c.text, final_in && final);
+      rc = long_push(R.d_text[s] + MK_FQ_CARRY, c.text, final_in && final);
       if (rc) { (void)hipStreamSynchronize(S); (void)hipStreamSynchronize(R.copy); snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", mk_last_error(e)); return rc; }
       continue;
     }
@@ -977,6 +982,10 @@ extern "C" int mk_sketch_push_bgzf_q(mk_engine *e, int fd, size_t size, const mk
 
 extern "C" int mk_sketch_push_bgzf_long(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int final, mk_bgzf_stats *st) {
   return mk_push_bgzf(e, fd, size, o, false, 0, 0, st, true, final);
+}
+
+extern "C" int mk_sketch_push_bgzf_long_q(mk_engine *e, int fd, size_t size, const mk_bgzf_opts *o, int32_t qmin, int final, mk_bgzf_stats *st) {
+  return mk_push_bgzf(e, fd, size, o, true, qmin, 0, st, true, final);
 }
 
 extern "C" const char *mk_bgzf_last_error(void) { return mk_bgzf_err; }
