@@ -886,6 +886,8 @@ const char *mk_bgzf_last_error(void); /* text of the calling thread's last faile
 /* the stream the engine's kernels are queued on now and its device, for work that must be ordered with them (staged rows are
  * flushed first).  MK_ERR_STATE with MK_OPT_SPLIT_CUS (two queues: no single stream orders with the scan). */
 int mk_engine_get_stream(mk_engine *e, void **hip_stream, int *device);
+/* for a route bound to the engine from outside (mk_sketch_push_gzip*): what mk_sketch_gunzip_repairs answers from now on */
+int mk_engine_note_gunzip_repairs(mk_engine *e, uint64_t repairs);
 
 /* ---- plain gzip FASTA inflated on the device, one wavefront per file (a directory of `.fna.gz` genomes; replaces one `zcat -fc`
  * child per file) ---------------------------------------------------------------------------------------------------------
@@ -958,6 +960,9 @@ int mk_sketch_batch_gz_status(mk_engine *e, uint32_t *status, uint32_t nfiles);
  *   mk_sketch_push_gzip_q ... and like mk_sketch_push_bgzf_q's, for the -n / -Q reader */
 #define MK_INFL_MISSED 9    /* a piece decoded past the start of the next one: the finder's candidate was no block start */
 #define MK_INFL_CAPACITY 10 /* a piece gave more than R times the compressed bytes it covers */
+/* With MK_GUNZIP_REPAIR (below) MK_INFL_MISSED no longer occurs on a one-member stream; MK_INFL_CAPACITY remains for the stream's
+ * last piece, for a piece that still meets its capacity after MK_GUNZIP_REPAIR_MERGES merges with the piece behind it, and for a
+ * piece or batch that would need 2^31 / 2^32 symbols. */
 /* eleven: (MK_GUNZIP_MEMBERS) behind a member's trailer and in front of the payload's end the bytes are not a gzip header with at
  * least one payload byte behind it: a wrong magic, CM != 8, reserved FLG bits, optional fields that run past the payload, or fewer
  * than 8 + 10 + 1 bytes left (zero padding, garbage) */
@@ -980,6 +985,24 @@ typedef struct mk_gunzip_opts {
  * member's start wherever a piece has seen that start.  The finder takes a member start whose first block is a dynamic one for a
  * piece start too.  Without the flag a second member is MK_INFL_TRAILING. */
 #define MK_GUNZIP_MEMBERS 1u
+/* REPAIR false piece starts instead of giving MK_INFL_MISSED.  The finder validates a block header and nothing
+ * behind it, so compressed data that holds the image of one gives a piece start that is none.  A piece whose own start is a true
+ * block start decodes true text for as long as it runs: when it passes the next piece's start it has proved that start false, and
+ * the block header at which it noticed is a true start.  With the flag the host walks every batch's piece table in stream order
+ * (the stream's first piece is confirmed; a piece is confirmed when the one in front is and stopped exactly at its start):
+ *   a confirmed piece with MK_INFL_MISSED   every start from its end up to the bit it stopped at is dropped, the piece keeps the
+ *                                           symbols it gave and ends at that bit, where a piece starts (a new one unless the
+ *                                           finder had the bit already);
+ *   a confirmed piece with MK_INFL_CAPACITY that is not the stream's last: the start behind it is dropped and the piece decoded
+ *                                           again with the capacity of the merged range, MK_GUNZIP_REPAIR_MERGES times at the most;
+ *   any other status of a confirmed piece   is the call's.  What an unconfirmed piece reported means nothing until it is
+ *                                           confirmed or dropped.
+ * New and re-sized pieces are decoded by one more launch of the same kernel, then the walk goes on; chain, resolve, CRC and the
+ * sink run once over the batch's final table.  Pieces, statistics and --timing report the final pieces.  A stream without a false
+ * start gives exactly the tables and text it gives without the flag and costs no launch.  Without the flag nothing changes.
+ * MK_GUNZIP_MEMBERS | MK_GUNZIP_REPAIR is MK_ERR_ARG: the member boundaries' two further MK_INFL_MISSED sites are not repaired yet. */
+#define MK_GUNZIP_REPAIR 2u
+#define MK_GUNZIP_REPAIR_MERGES 8u
 /* bit 63 of mk_gunzip_piece.start_bit (MK_GUNZIP_MEMBERS only): the piece starts at a member's header; the lower bits are 8 * the
  * header's first byte, in payload coordinates */
 #define MK_GUNZIP_PIECE_MEMBER ((uint64_t)1 << 63)
@@ -1003,6 +1026,8 @@ int mk_inflate_stream(mk_inflate *h, const uint8_t *comp, size_t comp_bytes, con
                       uint8_t *text_out, size_t cap, uint64_t *text_len, int32_t *status, mk_gunzip_pieces *pieces);
 /* members whose end the last mk_inflate_stream on h met and checked (with MK_INFL_OK: the members of the file; 1 without the flag) */
 int mk_inflate_stream_members(mk_inflate *h, uint64_t *members);
+/* piece starts the last mk_inflate_stream on h dropped (MK_GUNZIP_REPAIR; 0 without the flag and for a stream that needed none) */
+int mk_inflate_stream_repairs(mk_inflate *h, uint64_t *repairs);
 /* mk_inflate_status_text with a line for MK_INFL_BAD_MEMBER, the status only this route with MK_GUNZIP_MEMBERS gives (the older
  * function keeps answering "unknown status" above MK_INFL_CAPACITY, as its callers and tests know it) */
 const char *mk_gunzip_status_text(int status);
@@ -1040,6 +1065,9 @@ int mk_sketch_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_
 /* The same into a sketch begun with mk_sketch_begin_occ by DESIGN.md 4.21's rule: every batch's text goes to
  * mk_sketch_push_fastq_long_q_device with qmin.  Statuses and `final` as above. */
 int mk_sketch_push_gzip_long_q(mk_engine *e, int fd, size_t size, const mk_gunzip_opts *opts, int32_t qmin, int final, mk_gunzip_stats *st);
+/* piece starts the last mk_sketch_push_gzip, _q, _long or _long_q call on e dropped (MK_GUNZIP_REPAIR; mk_gunzip_stats has no room
+ * for the count).  st->pieces counts the final pieces. */
+int mk_sketch_gunzip_repairs(mk_engine *e, uint64_t *repairs);
 
 /* ---- a BATCH of single-member gzip genome files, many wavefronts per file ----------------------------------------
  * mk_sketch_batch_begin_gz with the decode above in place of one wavefront per file: a wave per span of S compressed bytes finds

@@ -203,6 +203,8 @@ def _load():
         "mk_inflate_stream": [vp, vp, C.c_size_t, C.POINTER(GzipInfoC), C.POINTER(GunzipOptsC), vp, C.c_size_t, C.POINTER(u64), C.POINTER(i32),
                               C.POINTER(GunzipPiecesC)],
         "mk_inflate_stream_members": [vp, C.POINTER(u64)],
+        "mk_inflate_stream_repairs": [vp, C.POINTER(u64)],
+        "mk_sketch_gunzip_repairs": [vp, C.POINTER(u64)],
         "mk_sketch_push_gzip": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), u64, C.POINTER(GunzipStatsC)],
         "mk_sketch_push_gzip_long": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), C.c_int, C.POINTER(GunzipStatsC)],
         "mk_sketch_push_gzip_long_q": [vp, C.c_int, C.c_size_t, C.POINTER(GunzipOptsC), C.c_int32, C.c_int, C.POINTER(GunzipStatsC)],
@@ -610,10 +612,11 @@ class Engine:
             raise err
         return st
 
-    def push_gzip(self, path, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0, members=False, qmin=None):
+    def push_gzip(self, path, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0, members=False, qmin=None, repair=False):
         """a single-member gzip FASTQ file into the sketch in progress (mk_sketch_push_gzip) -> GunzipStatsC; an inflate status or
-        a long line raises MkError(MK_ERR_FORMAT) with the statistics in .stats: the sketch is then to be begun anew"""
-        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), GunzipStatsC()
+        a long line raises MkError(MK_ERR_FORMAT) with the statistics in .stats: the sketch is then to be begun anew.  repair:
+        MK_GUNZIP_REPAIR, false piece starts are repaired; gunzip_repairs() says how many were dropped"""
+        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, _gunzip_flags(members, repair)), GunzipStatsC()
         fd = os.open(path, os.O_RDONLY)
         try:
             if qmin is None:
@@ -629,8 +632,15 @@ class Engine:
         return st
 
     def push_gzip_q(self, path, qmin=0, span_bytes=0, ratio=0, batch_spans=0, first_ordinal=0, members=False):
-        """the same for a sketch begun with begin_occ (mk_sketch_push_gzip_q): fastq2co's record rule and its -Q mask"""
+        """the same for a sketch begun with begin_occ (mk_sketch_push_gzip_q): fastq2co's record rule and its -Q mask (its
+        parameter list is pinned by tests/test_abi_gunzip_q.py: with the repair it is push_gzip(..., qmin=q, repair=True))"""
         return self.push_gzip(path, span_bytes, ratio, batch_spans, first_ordinal, members, qmin=qmin)
+
+    def gunzip_repairs(self):
+        """piece starts the last push_gzip* call on this engine dropped (mk_sketch_gunzip_repairs)"""
+        n = C.c_uint64(0)
+        _check(lib.mk_sketch_gunzip_repairs(self.h, C.byref(n)), self.h)
+        return n.value
 
     def push_bgzf_q(self, path, qmin=0, chunk_bytes=0, first_ordinal=0):
         """the same for a sketch begun with begin_occ (mk_sketch_push_bgzf_q): fastq2co's record rule and its -Q mask"""
@@ -698,11 +708,11 @@ class Engine:
         _check(lib.mk_sketch_fastq_long_frame_ms(self.h, C.byref(ms)), self.h)
         return ms.value
 
-    def push_gzip_long(self, path, span_bytes=0, ratio=0, batch_spans=0, members=False, final=True):
+    def push_gzip_long(self, path, span_bytes=0, ratio=0, batch_spans=0, members=False, final=True, repair=False):
         """a single-member gzip FASTQ file (members=True: a concatenation) into the MK_MODE_KOC sketch in progress by the long-read
         rule (mk_sketch_push_gzip_long) -> GunzipStatsC; an inflate status raises MkError(MK_ERR_FORMAT) with the statistics in
         .stats: the sketch is then to be finished, dropped and begun anew"""
-        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), GunzipStatsC()
+        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, _gunzip_flags(members, repair)), GunzipStatsC()
         fd = os.open(path, os.O_RDONLY)
         try:
             rc = lib.mk_sketch_push_gzip_long(self.h, fd, os.fstat(fd).st_size, C.byref(o), 1 if final else 0, C.byref(st))
@@ -752,10 +762,10 @@ class Engine:
         returns with the work queued: the memory stays untouched until the next call on this engine that waits"""
         _check(lib.mk_sketch_push_fastq_long_q_device(self.h, C.c_void_p(dev_ptr) if n else None, n, 1 if final else 0, qmin), self.h)
 
-    def push_gzip_long_q(self, path, qmin, span_bytes=0, ratio=0, batch_spans=0, members=False, final=True):
+    def push_gzip_long_q(self, path, qmin, span_bytes=0, ratio=0, batch_spans=0, members=False, final=True, repair=False):
         """push_gzip_long for the MK_MODE_OCC_SET sketch in progress, bases below qmin masked (mk_sketch_push_gzip_long_q) ->
         GunzipStatsC; statuses as push_gzip_long"""
-        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), GunzipStatsC()
+        o, st = GunzipOptsC(span_bytes, ratio, batch_spans, _gunzip_flags(members, repair)), GunzipStatsC()
         fd = os.open(path, os.O_RDONLY)
         try:
             rc = lib.mk_sketch_push_gzip_long_q(self.h, fd, os.fstat(fd).st_size, C.byref(o), qmin, 1 if final else 0, C.byref(st))
@@ -1406,6 +1416,12 @@ MK_BYREAD_MAX_PUSH = 8 << 20
 MK_INFL_OK, MK_INFL_BAD_BLOCK, MK_INFL_BAD_LENGTHS, MK_INFL_BAD_CODE, MK_INFL_BAD_DISTANCE, MK_INFL_INPUT, MK_INFL_OUTPUT_LEN, MK_INFL_CRC = range(8)
 MK_INFL_TRAILING, MK_INFL_MISSED, MK_INFL_CAPACITY, MK_INFL_BAD_MEMBER = 8, 9, 10, 11
 MK_GUNZIP_MEMBERS = 1
+MK_GUNZIP_REPAIR = 2
+MK_GUNZIP_REPAIR_MERGES = 8
+
+
+def _gunzip_flags(members, repair):
+    return (MK_GUNZIP_MEMBERS if members else 0) | (MK_GUNZIP_REPAIR if repair else 0)
 MK_GUNZIP_PIECE_MEMBER = 1 << 63
 MK_CRC_SLICE = 16384
 BGZF_FIELDS = ("in_off", "out_off", "in_len", "pay_off", "pay_len", "crc32", "isize")
@@ -1604,19 +1620,20 @@ class Inflate:
         self._check(rc)
         return out[:end].tobytes(), [(int(r.status), int(r.consumed), int(r.pos), int(r.crc32)) for r in res[:n]], pieces
 
-    def stream(self, comp, span_bytes=0, ratio=0, batch_spans=0, cap=None, guard=64, members=False):
+    def stream(self, comp, span_bytes=0, ratio=0, batch_spans=0, cap=None, guard=64, members=False, repair=False):
         """mk_inflate_stream over a whole gzip file (bytes) -> (text or None, MK_INFL_* status, [(start bit, text length) per piece],
         text length).  The text buffer has cap bytes (default: ISIZE, which is the text's length for texts below 4 GiB) between two
         guards of `guard` bytes, which must come back untouched.  members: MK_GUNZIP_MEMBERS, the file may be a concatenation of
         members; a piece is then (start bit, kind, text length) with kind 1 where it starts at a member's header, and the members
-        whose end was met come as a fifth value.  cap must then be given for a text that is not ISIZE bytes long."""
+        whose end was met come as a fifth value.  cap must then be given for a text that is not ISIZE bytes long.  repair:
+        MK_GUNZIP_REPAIR; the piece starts the repair dropped come as one more value, behind the others."""
         info = gzip_scan_stream(comp, raw=True)
         if info is None:
             raise MkError(MK_ERR_ARG, "not a single-member gzip file")
         b = np.frombuffer(bytes(comp), dtype=np.uint8)
         cap = int(info.isize) if cap is None else cap
         buf = np.full(cap + 2 * guard, 0xC3, dtype=np.uint8)
-        o, n, st, pieces = GunzipOptsC(span_bytes, ratio, batch_spans, MK_GUNZIP_MEMBERS if members else 0), C.c_uint64(0), C.c_int32(-1), GunzipPiecesC()
+        o, n, st, pieces = GunzipOptsC(span_bytes, ratio, batch_spans, _gunzip_flags(members, repair)), C.c_uint64(0), C.c_int32(-1), GunzipPiecesC()
         rc = lib.mk_inflate_stream(self.h, b.ctypes.data, len(b), C.byref(info), C.byref(o), buf.ctypes.data + guard, cap, C.byref(n),
                                    C.byref(st), C.byref(pieces))
         table = [(int(pieces.v[i].start_bit), int(pieces.v[i].text_len)) for i in range(pieces.n)]
@@ -1624,12 +1641,17 @@ class Inflate:
         self._check(rc)
         assert (buf[:guard] == 0xC3).all() and (buf[guard + cap:] == 0xC3).all(), "a write outside the text buffer"
         text = buf[guard:guard + n.value].tobytes() if st.value == 0 else None
+        out = (text, st.value, table, n.value)
         if members:
             table = [(s & ~MK_GUNZIP_PIECE_MEMBER, s >> 63, t) for s, t in table]
             nm = C.c_uint64(0)
             self._check(lib.mk_inflate_stream_members(self.h, C.byref(nm)))
-            return text, st.value, table, n.value, nm.value
-        return text, st.value, table, n.value
+            out = (text, st.value, table, n.value, nm.value)
+        if repair:
+            nr = C.c_uint64(0)
+            self._check(lib.mk_inflate_stream_repairs(self.h, C.byref(nr)))
+            out += (nr.value,)
+        return out
 
     def frame(self, text, final=True):
         """mk_fastq_frame_device -> (rows u8 [nrows * stride], stride, nrows, consumed, longest line, rc)"""

@@ -557,8 +557,13 @@ static int sketch_fastq_gunzip(ctx_t *c, const char *path) {
   c->nrows_total += gs.rows;
   c->t_last_push = now_s() - g_t0;
   if (g_opt.timing) {
-    char members[48] = ""; /* --gunzip-members: how many the file had */
+    char members[96] = ""; /* --gunzip-members: how many the file had; --gunzip-repair: the piece starts it dropped */
     if (g_opt.gunzip_opts.flags & MK_GUNZIP_MEMBERS) snprintf(members, sizeof members, ", \"members\": %u", gs.members);
+    if (g_opt.gunzip_opts.flags & MK_GUNZIP_REPAIR) {
+      uint64_t repairs = 0;
+      (void)mk_sketch_gunzip_repairs(e, &repairs);
+      snprintf(members + strlen(members), sizeof members - strlen(members), ", \"repairs\": %llu", (unsigned long long)repairs);
+    }
     printf("{\"input\": \"%s\", \"route\": \"device-gunzip\", \"pieces\": %llu, \"batches\": %llu, \"comp_bytes\": %llu, \"text_bytes\": %llu, \"rows\": %llu, "
            "\"find_ms\": %.3f, \"decode_ms\": %.3f, \"resolve_ms\": %.3f, \"frame_ms\": %.3f, \"read_s\": %.4f, \"route_total_s\": %.4f%s}\n",
            path, (unsigned long long)gs.pieces, (unsigned long long)gs.batches, (unsigned long long)gs.comp_bytes, (unsigned long long)gs.text_bytes,
@@ -698,8 +703,13 @@ static int sketch_fastq_long_inflate(ctx_t *c, const char *path) {
   if (rc != MK_OK) die("%s failed (%d): %s", c->occ ? "mk_sketch_push_gzip_long_q" : "mk_sketch_push_gzip_long", rc, mk_bgzf_last_error());
   c->t_last_push = now_s() - g_t0;
   if (g_opt.timing) {
-    char members[48] = ""; /* --gunzip-members: how many the file had */
+    char members[96] = ""; /* --gunzip-members: how many the file had; --gunzip-repair: the piece starts it dropped */
     if (g_opt.gunzip_opts.flags & MK_GUNZIP_MEMBERS) snprintf(members, sizeof members, ", \"members\": %u", gs.members);
+    if (g_opt.gunzip_opts.flags & MK_GUNZIP_REPAIR) {
+      uint64_t repairs = 0;
+      (void)mk_sketch_gunzip_repairs(e, &repairs);
+      snprintf(members + strlen(members), sizeof members - strlen(members), ", \"repairs\": %llu", (unsigned long long)repairs);
+    }
     printf("{\"input\": \"%s\", \"route\": \"%s\", \"source\": \"device-gunzip\", \"pieces\": %llu, \"batches\": %llu, \"comp_bytes\": %llu, "
            "\"text_bytes\": %llu, \"find_ms\": %.3f, \"decode_ms\": %.3f, \"resolve_ms\": %.3f, \"frame_ms\": %.3f, \"read_s\": %.4f, \"route_total_s\": %.4f%s}\n",
            path, long_route(c), (unsigned long long)gs.pieces, (unsigned long long)gs.batches, (unsigned long long)gs.comp_bytes, (unsigned long long)gs.text_bytes,

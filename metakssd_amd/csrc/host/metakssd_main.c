@@ -109,6 +109,7 @@ static void parse_dist_options(int argc, char **argv) {
     else if (!strcmp(argv[i], "--long-inflate-q")) o->long_reads_q = o->long_inflate_q = 1;
     else if (!strcmp(argv[i], "--device-gunzip")) o->device_gunzip = 1; /* dist -A and dist -n / -Q: a single-member .gz FASTQ inflated on the device */
     else if (!strcmp(argv[i], "--gunzip-members")) o->gunzip_opts.flags |= MK_GUNZIP_MEMBERS; /* ... and a concatenation of members */
+    else if (!strcmp(argv[i], "--gunzip-repair")) o->gunzip_opts.flags |= MK_GUNZIP_REPAIR; /* ... with false piece starts repaired instead of a fall-back */
     else if (!strcmp(argv[i], "--gunzip-span-bytes") && more) o->gunzip_opts.span_bytes = (uint32_t)atoll(argv[++i]);
     else if (!strcmp(argv[i], "--gunzip-ratio") && more) o->gunzip_opts.ratio = (uint32_t)atoll(argv[++i]);
     else if (!strcmp(argv[i], "--gunzip-batch-spans") && more) o->gunzip_opts.batch_spans = (uint32_t)atoll(argv[++i]);
@@ -142,6 +143,8 @@ static int dist_dispatch(void) {
   cli_opts *o = &g_opt;
   strlist *args = &o->args;
   int stage2_after = 0;
+  if ((o->gunzip_opts.flags & MK_GUNZIP_REPAIR) && (o->gunzip_opts.flags & MK_GUNZIP_MEMBERS))
+    die("--gunzip-repair does not go with --gunzip-members: member boundaries are not repaired yet (DESIGN.md 4.22)");
   if (o->long_reads_q) { /* the long route of the -n / -Q reader: what it cannot do is said before the device is touched */
     const char *sw = o->long_inflate_q ? "--long-inflate-q" : "--long-reads-q";
     if (o->long_reads) die("%s is the route of dist without -A: not with %s", sw, o->long_inflate ? "--long-inflate" : "--long-reads");

@@ -156,6 +156,7 @@ struct mk_engine {
   bool fq_q = false;      /* this sketch's long pushes are the quality-aware ones (chosen by the first) */
   int32_t fq_qmin = 0;    /* their -Q, the same in every push */
   bool fq_counted = false; /* a settled push of this sketch has given a record (decides the first-record exception) */
+  uint64_t gunzip_repairs = 0; /* of the last mk_sketch_push_gzip* call on this engine (mk_sketch_gunzip_repairs) */
 
   /* batches of small inputs (mk_sketch_batch_begin / _end): three contexts, two batches in flight, the third holds the results
    * handed out last */
@@ -880,6 +881,18 @@ extern "C" int mk_engine_get_stream(mk_engine *e, void **hip_stream, int *device
   if (e->copy_stream != e->stream) MK_HIP(e, hipStreamSynchronize(e->copy_stream)); /* (staged rows: their scan is queued, their copies are done) */
   *hip_stream = (void *)e->stream;
   if (device) *device = e->device;
+  return MK_OK;
+}
+
+extern "C" int mk_engine_note_gunzip_repairs(mk_engine *e, uint64_t repairs) {
+  if (!e) return MK_ERR_ARG;
+  e->gunzip_repairs = repairs;
+  return MK_OK;
+}
+
+extern "C" int mk_sketch_gunzip_repairs(mk_engine *e, uint64_t *repairs) {
+  if (!e || !repairs) return MK_ERR_ARG;
+  *repairs = e->gunzip_repairs;
   return MK_OK;
 }
 

@@ -20,6 +20,30 @@
  * inside its cap symbols, the chain inside its windows, the resolve inside the sum of the lengths the decode reported; every loop
  * consumes input bits or produces output symbols and is bounded by the two sizes.  Bound of each kernel: DESIGN.md 4.14.
  *
+ * MK_GUNZIP_REPAIR: the finder validates a header and nothing behind it, so an image of one inside compressed data
+ * is a piece start that is none.  Without the flag that is MK_INFL_MISSED; with it the host repairs the table after the decode
+ * launch, by an exact rule.  A piece whose start is a true block start decodes true text for as long as it runs, so when it runs
+ * past the next start it has proved that start false and stands, at the block header where it noticed, on a true start: `stop`.
+ * The walk goes over the batch's pieces in stream order and carries "this piece's start is confirmed" (the stream's first piece
+ * is; a piece is when the one in front is and stopped at its start with MK_INFL_OK; a batch's first piece through the last of the
+ * batch in front).  For a confirmed piece:
+ *   MK_INFL_OK        the next piece is confirmed
+ *   MK_INFL_MISSED    every start in [end, stop) leaves starts / kinds -- those of later batches too, which are found first; stop
+ *                     becomes a block-kind start unless it is one; the piece is MK_INFL_OK with end = stop and the symbols it gave;
+ *                     what the dropped pieces reported is discarded
+ *   MK_INFL_CAPACITY  not the stream's last piece: the decode cannot say where it was (a stored block refuses at its header), so
+ *                     the next start is dropped and the piece decoded again from its start with R * (the merged range), at most
+ *                     MK_GUNZIP_REPAIR_MERGES times; a merge with a true start is still correct, the bound only keeps one wave
+ *                     from being handed the whole file
+ *   anything else     is the call's status.  A status of an unconfirmed piece means nothing until it is confirmed or dropped.
+ * A new or re-sized piece is decoded by one launch of mk_gun_decode_kernel<false> over a table of that piece alone, its symbols at
+ * the tail of the symbol buffer (which grows with its content kept); then the walk goes on from it.  Every launch follows a dropped
+ * start, so there are fewer launches than starts.  A piece whose status came from compressed bytes that had not been uploaded yet
+ * (stop behind them) is decoded again once more have arrived.  Chain, resolve, CRC and sink run once, over the final table; a
+ * resumed piece at or behind the batch's bit_end is the next batch's.  Safety: a table entry of this path has the cap and symbol
+ * range the first launch's entries have (R * covered bytes, inside nsyms <= syms_cap), so the kernel's bounds hold unchanged.
+ * The two further MK_INFL_MISSED sites of the <true> decode are not repaired: both flags together are MK_ERR_ARG.
+ *
  * MK_GUNZIP_MEMBERS: the payload may hold further members, each behind the trailer of the one in front.  The
  * <true> instances of finder and decode are for it; the <false> ones are the kernels described above, unchanged.
  *   finder     a second rule at byte-aligned lanes: a gzip header of at most MK_GUN_HDR_MAX bytes and behind it a dynamic block
@@ -475,6 +499,7 @@ struct mk_gun_result {
   int32_t status = MK_INFL_OK;
   int64_t bad_piece = -1;
   uint64_t text_len = 0, npieces = 0, nbatches = 0, members = 0;
+  uint64_t repairs = 0; /* MK_GUNZIP_REPAIR: piece starts dropped */
   double find_ms = 0, decode_ms = 0, resolve_ms = 0, t_read_s = 0;
 };
 
@@ -539,6 +564,8 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
   const uint64_t pay_len = info.pay_len, f0 = info.pay_off & ~(uint64_t)15u, total = size - f0; /* the device holds file bytes [f0, size) */
   const uint32_t shift = (uint32_t)(info.pay_off - f0), S = G.S;
   const bool members = opts && (opts->flags & MK_GUNZIP_MEMBERS);
+  const bool repair = opts && (opts->flags & MK_GUNZIP_REPAIR);
+  if (members && repair) { snprintf(R.err, sizeof R.err, "MK_GUNZIP_MEMBERS | MK_GUNZIP_REPAIR: member boundaries are not repaired yet"); return MK_ERR_ARG; }
   const uint64_t ahead = members ? 4096u + MK_GUN_HDR_MAX : 4096u; /* bytes behind a span the finder may read */
   if (!info.is_single || info.pay_off + pay_len + 8u != size || pay_len == 0) { snprintf(R.err, sizeof R.err, "not a single-member gzip file"); return MK_ERR_ARG; }
   const uint64_t NS = (pay_len + S - 1) / S, NB = (NS + G.batch - 1) / G.batch;
@@ -618,8 +645,8 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     while (idx_end < starts.size() && starts[idx_end] < bit_end) idx_end++;
     if (idx_end == idx) continue;
     while (idx_end == starts.size() && found < NB) { rc = find_batch(found++); if (rc) return rc; } /* where the batch's last piece ends */
-    const uint32_t np = (uint32_t)(idx_end - idx);
-    const bool final = idx_end == starts.size();
+    uint32_t np = (uint32_t)(idx_end - idx);
+    bool final = idx_end == starts.size();
     MK_GUN_HIP(mk_grow(&R.h_pieces, &R.hpieces_cap, np, true));
     MK_GUN_HIP(mk_grow(&R.d_pieces, &R.pieces_cap, np, false));
     uint64_t nsyms = 0, nslots = 0;
@@ -663,6 +690,130 @@ static int mk_gun_stream(mk_gun_run &R, uint64_t size, const mk_gzip_info &info,
     MK_GUN_HIP(hipEventElapsedTime(&ms, R.ev_t[2], R.ev_t[3]));
     res.decode_ms += ms;
     res.nbatches++;
+    if (repair) { /* the walk of the file's header comment.  T mirrors starts[idx, idx + T.size()) */
+      std::vector<mk_gun_piece> T(R.h_pieces, R.h_pieces + np);
+      std::vector<uint8_t> decoded(np, 1), merges(np, 0);
+      std::vector<uint64_t> upl(np, up); /* file bytes the device held when the piece was decoded */
+      auto drop = [&](uint32_t a, uint32_t b) { /* T[a, b) */
+        T.erase(T.begin() + a, T.begin() + b);
+        decoded.erase(decoded.begin() + a, decoded.begin() + b);
+        merges.erase(merges.begin() + a, merges.begin() + b);
+        upl.erase(upl.begin() + a, upl.begin() + b);
+      };
+      auto know_next = [&](uint64_t i) -> int { /* starts[i + 1] is known, or the stream has no start behind starts[i] */
+        while (i + 1 >= starts.size() && found < NB) { const int r = find_batch(found++); if (r) return r; }
+        return MK_OK;
+      };
+      uint32_t k = 0; /* pieces in front of T[k] are confirmed and final */
+      for (;;) {
+        int64_t redo = -1; /* the piece the next launch decodes */
+        bool resize = false, stands = false;
+        for (; k < T.size() && redo < 0 && !stands; k++) {
+          mk_gun_piece &P = T[k];
+          const uint64_t gi = idx + k;
+          if (!decoded[k]) { redo = k; resize = true; break; }
+          if (!P.status) continue;
+          if (upl[k] < total && P.stop > 8u * (upl[k] - std::min<uint64_t>(upl[k], shift))) { /* it ran into bytes that had not arrived: once more, with more of them */
+            rc = ensure_uploaded(up + stage_bytes);
+            if (rc) return rc;
+            redo = k;
+            break;
+          }
+          if (P.status == MK_INFL_MISSED && P.end != MK_GUN_NONE && P.stop > P.end) {
+            while (found < NB && 8u * found * G.batch * S <= P.stop) { rc = find_batch(found++); if (rc) return rc; } /* every candidate in front of stop is known */
+            size_t a = gi + 1, b = a;
+            while (b < starts.size() && starts[b] < P.stop) b++;
+            res.repairs += b - a;
+            starts.erase(starts.begin() + a, starts.begin() + b);
+            kinds.erase(kinds.begin() + a, kinds.begin() + b);
+            const bool known = a < starts.size() && starts[a] == P.stop;
+            if (!known) { starts.insert(starts.begin() + a, P.stop); kinds.insert(kinds.begin() + a, 0); }
+            uint32_t d = k + 1;
+            while (d < T.size() && T[d].start < P.stop) d++;
+            drop(k + 1, d);
+            mk_gun_piece &Q = T[k]; /* (P may have moved) */
+            Q.status = MK_INFL_OK;
+            Q.end = Q.stop;
+            if (!known && Q.stop < bit_end) { /* the resumed piece is this batch's */
+              rc = know_next(a);
+              if (rc) return rc;
+              mk_gun_piece N;
+              memset(&N, 0, sizeof N);
+              N.start = Q.stop;
+              N.end = a + 1 < starts.size() ? starts[a + 1] : MK_GUN_NONE;
+              T.insert(T.begin() + k + 1, N);
+              decoded.insert(decoded.begin() + k + 1, 0);
+              merges.insert(merges.begin() + k + 1, 0);
+              upl.insert(upl.begin() + k + 1, 0);
+            }
+            continue;
+          }
+          if (P.status == MK_INFL_CAPACITY && P.end != MK_GUN_NONE && merges[k] < MK_GUNZIP_REPAIR_MERGES) {
+            rc = know_next(gi + 1);
+            if (rc) return rc;
+            starts.erase(starts.begin() + gi + 1);
+            kinds.erase(kinds.begin() + gi + 1);
+            res.repairs++;
+            if (k + 1 < T.size()) drop(k + 1, k + 2);
+            mk_gun_piece &Q = T[k];
+            Q.end = gi + 1 < starts.size() ? starts[gi + 1] : MK_GUN_NONE;
+            merges[k]++;
+            redo = k;
+            resize = true;
+            break;
+          }
+          stands = true; /* the call's status */
+          break;
+        }
+        if (redo < 0) break; /* every piece is confirmed, or one's status stands */
+        mk_gun_piece &P = T[redo];
+        if (resize) { /* its symbols at the tail of the buffer */
+          const uint64_t covered = (P.end == MK_GUN_NONE ? pay_len : (P.end + 7u) >> 3) - (P.start >> 3);
+          const uint64_t cap = (uint64_t)G.ratio * covered;
+          if (cap >= ((uint64_t)1 << 31) || nsyms + cap >= ((uint64_t)1 << 32)) {
+            (void)hipStreamSynchronize(R.S); (void)hipStreamSynchronize(R.copy);
+            res.status = MK_INFL_CAPACITY; res.bad_piece = (int64_t)(idx + redo);
+            return MK_OK;
+          }
+          P.cap = (uint32_t)cap;
+          P.sym_off = nsyms;
+          nsyms += (cap + 7u) & ~(uint64_t)7u;
+          if (nsyms > R.syms_cap) { /* grow with the content kept: the other pieces' symbols stay where they are */
+            const uint64_t c = nsyms + nsyms / 8 + 256;
+            uint16_t *nw = nullptr;
+            MK_GUN_HIP(mk_dev_alloc(&nw, (size_t)c * sizeof(uint16_t)));
+            const hipError_t cr = hipMemcpyAsync(nw, R.d_syms, (size_t)P.sym_off * sizeof(uint16_t), hipMemcpyDeviceToDevice, R.S);
+            const hipError_t sr = hipStreamSynchronize(R.S);
+            (void)hipFree(R.d_syms);
+            R.d_syms = nw;
+            R.syms_cap = c;
+            MK_GUN_HIP(cr);
+            MK_GUN_HIP(sr);
+          }
+        }
+        P.status = 0; P.len = 0; P.stop = 0;
+        rc = ensure_uploaded(P.end == MK_GUN_NONE ? total : shift + (P.end >> 3) + 4096u);
+        if (rc) return rc;
+        upl[redo] = up;
+        decoded[redo] = 1;
+        R.h_pieces[0] = P;
+        MK_GUN_HIP(hipMemcpyAsync(R.d_pieces, R.h_pieces, sizeof(mk_gun_piece), hipMemcpyHostToDevice, R.S));
+        MK_GUN_HIP(hipEventRecord(R.ev_t[2], R.S));
+        hipLaunchKernelGGL(mk_gun_decode_kernel<false>, dim3(1), dim3(64 * MK_INFL_WAVES), 0, R.S, (const uint8_t *)R.d_comp, shift, pay_len, R.d_pieces, 1u, R.d_syms, R.d_mems);
+        MK_GUN_HIP(hipGetLastError());
+        MK_GUN_HIP(hipEventRecord(R.ev_t[3], R.S));
+        MK_GUN_HIP(hipMemcpyAsync(R.h_pieces, R.d_pieces, sizeof(mk_gun_piece), hipMemcpyDeviceToHost, R.S));
+        MK_GUN_HIP(hipStreamSynchronize(R.S));
+        MK_GUN_HIP(hipEventElapsedTime(&ms, R.ev_t[2], R.ev_t[3]));
+        res.decode_ms += ms;
+        T[redo] = R.h_pieces[0];
+        k = (uint32_t)redo;
+      }
+      np = (uint32_t)T.size(); /* never more than it was: a resumed piece takes the place of a dropped one */
+      memcpy(R.h_pieces, T.data(), (size_t)np * sizeof(mk_gun_piece));
+      idx_end = idx + np;
+      final = idx_end == starts.size();
+    }
     uint64_t ntext = 0;
     uint32_t nrec = 0;
     for (uint32_t k = 0; k < np; k++) {
@@ -809,6 +960,7 @@ extern "C" int mk_inflate_stream(mk_inflate *h, const uint8_t *comp, size_t comp
   *status = res.status;
   h->inflate_ms = res.find_ms + res.decode_ms + res.resolve_ms;
   h->stream_members = res.members;
+  h->stream_repairs = res.repairs;
   if (pieces && !tab.empty()) {
     pieces->v = (mk_gunzip_piece *)malloc(tab.size() * sizeof(mk_gunzip_piece));
     if (!pieces->v) return MK_ERR_NOMEM;
@@ -825,6 +977,12 @@ extern "C" int mk_inflate_stream_members(mk_inflate *h, uint64_t *members) {
   return MK_OK;
 }
 
+extern "C" int mk_inflate_stream_repairs(mk_inflate *h, uint64_t *repairs) {
+  if (!h || !repairs) return MK_ERR_ARG;
+  *repairs = h->stream_repairs;
+  return MK_OK;
+}
+
 /* both readers' route: occ == false is mk_fastq_frame's rule (-A), occ == true mk_fastq_frame_q's (quality mask qmin), one row a
  * record.  What the second needs from the sink: the file's record count (stats.rows), which decides the first-record exception -- it can only arise in the last slice of the last batch, whose text [t0, e1) is then the
  * whole file: everything in front of it went through the carry, possibly in front of an empty batch. */
@@ -834,6 +992,7 @@ static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts 
   memset(&stats, 0, sizeof stats);
   stats.bad_piece = -1;
   if (st) *st = stats;
+  (void)mk_engine_note_gunzip_repairs(e, 0);
   const double t_begin = mk_now_s();
   mk_gzip_info info;
   int rc = mk_gzip_scan_stream(fd, nullptr, size, &info);
@@ -905,6 +1064,7 @@ static int mk_push_gzip(mk_engine *e, int fd, size_t size, const mk_gunzip_opts 
   stats.find_ms = res.find_ms; stats.decode_ms = res.decode_ms; stats.resolve_ms = res.resolve_ms; stats.t_read_s = res.t_read_s;
   stats.bad_piece = res.bad_piece; stats.bad_status = res.status; stats.members = (uint32_t)std::min<uint64_t>(res.members, 0xffffffffu);
   stats.t_total_s = mk_now_s() - t_begin;
+  (void)mk_engine_note_gunzip_repairs(e, res.repairs);
   if (st) *st = stats;
   if (rc == MK_ERR_FORMAT && long_line) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "a FASTQ line of 4095 characters or more"); return rc; }
   if (rc) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", R.err); return rc; }
@@ -927,6 +1087,7 @@ static int mk_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_
   memset(&stats, 0, sizeof stats);
   stats.bad_piece = -1;
   if (st) *st = stats;
+  (void)mk_engine_note_gunzip_repairs(e, 0);
   const double t_begin = mk_now_s();
   mk_gzip_info info;
   int rc = mk_gzip_scan_stream(fd, nullptr, size, &info);
@@ -972,6 +1133,7 @@ static int mk_push_gzip_long(mk_engine *e, int fd, size_t size, const mk_gunzip_
   stats.find_ms = res.find_ms; stats.decode_ms = res.decode_ms; stats.resolve_ms = res.resolve_ms; stats.t_read_s = res.t_read_s;
   stats.bad_piece = res.bad_piece; stats.bad_status = res.status; stats.members = (uint32_t)std::min<uint64_t>(res.members, 0xffffffffu);
   stats.t_total_s = mk_now_s() - t_begin;
+  (void)mk_engine_note_gunzip_repairs(e, res.repairs);
   if (st) *st = stats;
   if (rc) { snprintf(mk_bgzf_err, sizeof mk_bgzf_err, "%s", R.err); return rc; }
   if (res.status) {

@@ -507,6 +507,7 @@ struct mk_inflate {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   double inflate_ms = 0.0, frame_ms = 0.0;
   uint64_t stream_members = 0; /* of the last mk_inflate_stream */
+  uint64_t stream_repairs = 0; /* ... and the starts its repair dropped (MK_GUNZIP_REPAIR) */
   char err[256] = {0};
 };
 
